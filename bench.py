@@ -6,9 +6,17 @@ A "step" is one ``HookedViT.run_with_cache`` pass (ALL hooks, 214 cache entries)
 @224 over one batch of 512 synthetic images per GPU, bf16 storage (BASELINE.json configs[1]),
 inputs already resident in HBM.  With N > 1 (one process per GPU, launched by torch.distributed.run)
 the image batches are sharded across ranks with no data-path collective (weak scaling).
-Rank 0 prints ONE JSON line; ``value`` is the whole-job images/s.
+Rank 0 prints ONE JSON line; ``value`` is the whole-job images/s, ``ms_per_step`` the wall time of one timed step.
 
-Extra objects on the same line:
+A plain run sets up, warms up, times the K steps and prints the line: nothing else runs on the GPU or the host.
+
+    --dump-outputs DIR   after the timed steps, what the last one returned -- the output as DIR/output.npy and every cache entry
+                         as DIR/cache.<hook name>.npy, float32 -- a fixed, seeded sample of the elements of a large array (see
+                         dump_outputs), 29 MB in all; the inputs are seeded, so two builds run with the same arguments can be
+                         compared array for array
+    --full               also the secondary measurements below (per-kernel figures, SAE legs, the L/14 leg, CPU baselines)
+
+Extra objects on the same line with --full:
   roofline      dominant kernel (the MFMA GEMM family): algorithmic FLOPs per launch / average launch
                 duration measured with HIP events on the launch stream inside the timed region
   kernels       the same live measurement for the other kernel families (attention, layernorm)
@@ -42,8 +50,13 @@ TAP_BYTES_PER_IMAGE_B32_BF16 = 20.34e6
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: per-kernel figures, SAE legs, the L/14 leg, CPU baselines (the --no-* options "
+                         "below and --sae-parallel / --leg-timeout apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/*.npy (float32; large arrays as a fixed, seeded sample)")
     ap.add_argument("--batch", type=int, default=512, help="images per GPU per step")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -60,7 +73,40 @@ def parse():
                     help="under torchrun: seconds the secondary legs (SAE, L/14) may take before the main line is printed without them")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="A/B runs only (needs --allow-overrides): pv_debug_set_tuning(KEY, VALUE) before measuring")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
+
+
+DUMP_SAMPLE = 32768            # elements kept of a cache entry larger than this (--dump-outputs)
+DUMP_OUTPUT_WHOLE = 1 << 20    # the model output is written whole up to this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, out, cache) -> dict:
+    """Writes the output and every cache entry of one step to ``path`` as float32 .npy files.  An array above its limit
+    (DUMP_OUTPUT_WHOLE for the output, DUMP_SAMPLE for a cache entry) is written as the 1-D sample at DUMP_SAMPLE flat indices
+    (row-major, sorted, drawn with replacement) from a generator seeded by the array's name: the same elements whatever the
+    build.  Returns {file name: shape written}."""
+    import zlib
+    arrays = [("output", out, DUMP_OUTPUT_WHOLE)] + [(f"cache.{k}", v, DUMP_SAMPLE) for k, v in cache.items()]
+    os.makedirs(path, exist_ok=True)
+    written, total = {}, 0
+    for name, t, limit in arrays:
+        t = t.detach()
+        if t.numel() > limit:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, t.numel(), DUMP_SAMPLE))
+            t = torch.take(t, torch.from_numpy(idx).to(t.device))
+        arr = t.float().cpu().numpy()
+        total += arr.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(path, name + ".npy"), arr)
+        written[name + ".npy"] = list(arr.shape)
+    return written
 
 
 def _median(xs):
@@ -332,6 +378,49 @@ def l14_pattern_leg(dev, dist, batch: int = 128, steps: int = 10, warmup: int = 
                          "hbm_GBps_algorithmic": round(ips / world * bytes_img / 1e9, 1)}}
 
 
+def kernel_figures(N, a, ms_per_step: float, peak_tf: float) -> tuple:
+    """--full: the roofline of the dominant kernel family from the HIP events of the timed region, and the other families' figures
+    from the two untimed steps after it.  Returns (roofline, kernels)."""
+    gemm = N.prof_read("gemm")
+    attn = N.prof_read("attention")
+    ln = N.prof_read("layernorm")
+    gemm_tf = gemm["flops"] / max(gemm["ms"], 1e-9) / 1e9
+    roofline = {
+        "kernel": "gemm_kernel_v8 / v7 family (bf16 MFMA GEMM, 320x256 tile, fused bias / activation / residual / tap-store epilogues; v8 = the persistent form, one workgroup per CU walking its tiles, where a launch has more tiles than CUs; + the patch-embed and head GEMMs)",
+        "bound": "mfma", "achieved": round(gemm_tf, 2), "peak": peak_tf, "unit": "TFLOP/s",
+        "frac": round(gemm_tf / peak_tf, 4),
+        "launches": gemm["launches"], "avg_launch_us": round(gemm["ms"] * 1e3 / max(gemm["launches"], 1), 2),
+        "flops_per_launch": gemm["flops"] / max(gemm["launches"], 1),
+        "hbm_GBps_algorithmic": round(gemm["bytes"] / max(gemm["ms"], 1e-9) / 1e6, 1),
+        "share_of_step": round(gemm["ms"] / (ms_per_step * a.steps), 4),
+        "traffic": None,
+    }
+    # per GEMM instance: both roofs (the bf16 MFMA peak and the HBM floor of its own algorithmic bytes), max of the two fractions --
+    # the O-projection and MLP-1 move the most bytes per flop of the four (VERDICT r3 item 3)
+    inst = {}
+    for nm, tag in N.GEMM_TAGS.items():
+        g_ = N.prof_read_tag("gemm", tag)
+        if g_["launches"]:
+            tf_ = g_["flops"] / max(g_["ms"], 1e-9) / 1e9
+            gb_ = g_["bytes"] / max(g_["ms"], 1e-9) / 1e6
+            inst[nm] = {"launches": g_["launches"], "avg_launch_us": round(g_["ms"] * 1e3 / g_["launches"], 2),
+                        "TFLOPs": round(tf_, 1), "frac_mfma": round(tf_ / peak_tf, 4), "GBps_algorithmic": round(gb_, 1),
+                        "frac_hbm": round(gb_ / PEAK_HBM_GBS, 4), "frac": round(max(tf_ / peak_tf, gb_ / PEAK_HBM_GBS), 4)}
+    roofline["instances"] = inst
+    tr = pmc_traffic("gemm_kernel") if a.dtype == "bf16" and a.batch == 512 else None
+    if tr is not None:
+        roofline["traffic"] = tr["bytes_per_launch"]
+        roofline["traffic_source"] = f"{tr['source']} ({tr['kernel']}); algorithmic bytes per launch = {gemm['bytes'] / max(gemm['launches'], 1):.4g}"
+    kernels = {}
+    for nm, k in (("attention", attn), ("layernorm", ln)):
+        kernels[nm] = {
+            "bound": "hbm", "achieved": round(k["bytes"] / max(k["ms"], 1e-9) / 1e6, 1), "peak": PEAK_HBM_GBS,
+            "unit": "GB/s", "frac": round(k["bytes"] / max(k["ms"], 1e-9) / 1e6 / PEAK_HBM_GBS, 4),
+            "launches": k["launches"], "avg_launch_us": round(k["ms"] * 1e3 / max(k["launches"], 1), 2),
+            "share_of_step": round(k["ms"] / (ms_per_step * 2), 4), "sampled": "2 untimed steps after the timed region"}
+    return roofline, kernels
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -392,26 +481,33 @@ def main():
     with torch.no_grad():
         for _ in range(a.warmup):
             out, cache = step()
-            n_keys = len(cache)
             del out, cache
-        N.prof_reset()
-        N.prof_enable(True, kinds=("gemm",))      # the timed region carries HIP events around the dominant kernel only
+        if a.full:
+            N.prof_reset()
+            N.prof_enable(True, kinds=("gemm",))      # the timed region carries HIP events around the dominant kernel only
         barrier()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
+        for i in range(a.steps):
             out, cache = step()
-            del out, cache
+            if i + 1 < a.steps:
+                del out, cache                        # (the last step's arrays are what --dump-outputs writes)
         barrier()
         elapsed = time.perf_counter() - t0
-        N.prof_enable(False)
-        # the secondary kernels' figures come from two extra, UNTIMED steps (every event pair costs stream time)
-        N.prof_enable(True, kinds=("attention", "layernorm"))
-        for _ in range(2):
-            out, cache = step()
-            del out, cache
-        torch.cuda.synchronize(dev)
-        N.prof_enable(False)
-    assert n_keys == 214 and model.last_run_native
+        if a.full:
+            N.prof_enable(False)
+        n_keys = len(cache)
+        assert n_keys == 214 and model.last_run_native
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, out, cache)
+        del out, cache
+        if a.full:
+            # the secondary kernels' figures come from two extra, UNTIMED steps (every event pair costs stream time)
+            N.prof_enable(True, kinds=("attention", "layernorm"))
+            for _ in range(2):
+                out, cache = step()
+                del out, cache
+            torch.cuda.synchronize(dev)
+            N.prof_enable(False)
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -420,45 +516,9 @@ def main():
     images_total = a.batch * a.steps * world
     value = images_total / elapsed
     ms_per_step = elapsed / a.steps * 1e3
-
-    gemm = N.prof_read("gemm")
-    attn = N.prof_read("attention")
-    ln = N.prof_read("layernorm")
     peak_tf = PEAK_BF16_TFLOPS if a.dtype == "bf16" else PEAK_F32_TFLOPS
-    gemm_tf = gemm["flops"] / max(gemm["ms"], 1e-9) / 1e9
-    roofline = {
-        "kernel": "gemm_kernel_v8 / v7 family (bf16 MFMA GEMM, 320x256 tile, fused bias / activation / residual / tap-store epilogues; v8 = the persistent form, one workgroup per CU walking its tiles, where a launch has more tiles than CUs; + the patch-embed and head GEMMs)",
-        "bound": "mfma", "achieved": round(gemm_tf, 2), "peak": peak_tf, "unit": "TFLOP/s",
-        "frac": round(gemm_tf / peak_tf, 4),
-        "launches": gemm["launches"], "avg_launch_us": round(gemm["ms"] * 1e3 / max(gemm["launches"], 1), 2),
-        "flops_per_launch": gemm["flops"] / max(gemm["launches"], 1),
-        "hbm_GBps_algorithmic": round(gemm["bytes"] / max(gemm["ms"], 1e-9) / 1e6, 1),
-        "share_of_step": round(gemm["ms"] / (ms_per_step * a.steps), 4),
-        "traffic": None,
-    }
-    # per GEMM instance: both roofs (the bf16 MFMA peak and the HBM floor of its own algorithmic bytes), max of the two fractions --
-    # the O-projection and MLP-1 move the most bytes per flop of the four
-    inst = {}
-    for nm, tag in N.GEMM_TAGS.items():
-        g_ = N.prof_read_tag("gemm", tag)
-        if g_["launches"]:
-            tf_ = g_["flops"] / max(g_["ms"], 1e-9) / 1e9
-            gb_ = g_["bytes"] / max(g_["ms"], 1e-9) / 1e6
-            inst[nm] = {"launches": g_["launches"], "avg_launch_us": round(g_["ms"] * 1e3 / g_["launches"], 2),
-                        "TFLOPs": round(tf_, 1), "frac_mfma": round(tf_ / peak_tf, 4), "GBps_algorithmic": round(gb_, 1),
-                        "frac_hbm": round(gb_ / PEAK_HBM_GBS, 4), "frac": round(max(tf_ / peak_tf, gb_ / PEAK_HBM_GBS), 4)}
-    roofline["instances"] = inst
-    tr = pmc_traffic("gemm_kernel") if a.dtype == "bf16" and a.batch == 512 else None
-    if tr is not None:
-        roofline["traffic"] = tr["bytes_per_launch"]
-        roofline["traffic_source"] = f"{tr['source']} ({tr['kernel']}); algorithmic bytes per launch = {gemm['bytes'] / max(gemm['launches'], 1):.4g}"
-    kernels = {}
-    for nm, k in (("attention", attn), ("layernorm", ln)):
-        kernels[nm] = {
-            "bound": "hbm", "achieved": round(k["bytes"] / max(k["ms"], 1e-9) / 1e6, 1), "peak": PEAK_HBM_GBS,
-            "unit": "GB/s", "frac": round(k["bytes"] / max(k["ms"], 1e-9) / 1e6 / PEAK_HBM_GBS, 4),
-            "launches": k["launches"], "avg_launch_us": round(k["ms"] * 1e3 / max(k["launches"], 1), 2),
-            "share_of_step": round(k["ms"] / (ms_per_step * 2), 4), "sampled": "2 untimed steps after the timed region"}
+    if a.full:
+        roofline, kernels = kernel_figures(N, a, ms_per_step, peak_tf)
     per_gpu = value / world
     whole = {
         "flop_frac_of_mfma_peak": round(per_gpu * FLOP_PER_IMAGE_B32 / (peak_tf * 1e12), 4),
@@ -473,7 +533,7 @@ def main():
         "config": {"workload": f"CLIP ViT-B/32 run_with_cache, all 214 hooks tapped to the HBM arena, "
                                f"bs={a.batch}/GPU, {a.dtype}", "images_per_gpu_per_step": a.batch,
                    "cache_keys": n_keys, "parallelism": f"image-batch sharding x{world}, no data-path collective"},
-        "roofline": roofline, "kernels": kernels, "whole_forward": whole,
+        **({"roofline": roofline, "kernels": kernels} if a.full else {}), "whole_forward": whole, "full": a.full,
         "overrides": {"env": pv_env, "tuning": N.get_tuning("any"), "tune": list(a.tune)},
     }
     if backend != "nccl":
@@ -498,7 +558,7 @@ def main():
             os._exit(0)
 
     wd = None
-    if world > 1:
+    if world > 1 and a.full:
         wd = threading.Timer(a.leg_timeout, emergency)
         wd.daemon = True
         wd.start()
@@ -513,7 +573,7 @@ def main():
             sys.stderr.write(f"[bench rank {rank}] leg {name} failed: {type(e).__name__}: {e}\n")
             return {"error": f"{type(e).__name__}: {e}"}
 
-    if not a.no_sae:
+    if a.full and not a.no_sae:
         from vit_prisma_amd.sae.bench_leg import sae_bench_leg, sae_end_to_end_leg
         del model, images
         torch.cuda.empty_cache()
@@ -568,12 +628,12 @@ def main():
             if world == 1 and not a.no_cpu_baseline:
                 sae["cpu_baseline"] = sae_cpu_baseline_torch(10.0)
                 sae["cpu_baseline"]["numpy_oracle"] = sae_cpu_baseline(6.0)
-    if not a.no_l14:
+    if a.full and not a.no_l14:
         torch.cuda.empty_cache()
         l14 = leg("l14_336_pattern", lambda: l14_pattern_leg(dev, dist, batch=a.l14_batch))
         if rank == 0:
             line["l14_336_pattern"] = l14
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_torch(a.cpu_seconds)
         line["cpu_baseline"]["numpy_oracle"] = cpu_baseline(min(a.cpu_seconds, 8.0))
         line["speedup_vs_cpu_baseline"] = round(value / line["cpu_baseline"]["value"], 1)

@@ -6,12 +6,17 @@
   geometric_median.npz              points, the reference's compute_geometric_median(points, maxiter=100).median
                                     (sae/training/geometric_median.py:23-86)
     python tests/golden/gen_golden_sae_ckpt.py
+
+The reconstruction in io.pt is computed with MKL's conditional numerical reproducibility (MKL_CBWR=COMPATIBLE): the same bits
+on any x86 CPU, which the test's bit-for-bit comparison relies on.
 """
 import os
 import sys
 
-import numpy as np
-import torch
+os.environ["MKL_CBWR"] = "COMPATIBLE"         # (before MKL is loaded)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))

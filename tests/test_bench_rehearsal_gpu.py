@@ -23,7 +23,7 @@ def test_eight_rank_bench_line_completes_on_one_gpu():
         del env[k]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "64",
-           "--l14-batch", "8", "--no-cpu-baseline", "--leg-timeout", "1200"]
+           "--full", "--l14-batch", "8", "--no-cpu-baseline", "--leg-timeout", "1200"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1400)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])

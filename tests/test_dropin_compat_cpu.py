@@ -1,8 +1,5 @@
 """Drop-in loose ends (north_star: "existing Prisma notebooks and SAE configs drop in unchanged"):
-  * ``vit_prisma_amd.install_as("vit_prisma")``: the reference's import paths resolve to this build, and the REFERENCE'S OWN
-    offline tests (tests/test_hooks.py, test_cache_hook_names.py, test_weight_properties.py,
-    tests/sae/test_load_VisionModelSAERunnerConfig.py) pass against it unmodified (build container only: they are run
-    from /root/reference, never copied)
+  * ``vit_prisma_amd.install_as("vit_prisma")``: the reference's import paths resolve to this build
   * checkpoints written by the reference (pickled vit_prisma.sae.config.VisionModelSAERunnerConfig) load, in the
     reference's argument order, and reproduce the reference module's output bit for bit
   * VisionSAETrainer.run() end to end on the tiny model, geometric-median b_dec initialisation against the reference's
@@ -22,8 +19,6 @@ from vit_prisma_amd.sae.geometric_median import compute_geometric_median
 from vit_prisma_amd.synth import ARCHS, synth_images, synth_vit_state
 
 from conftest import GOLDEN, ROOT
-
-REF_TESTS = "/root/reference/tests"
 
 
 def test_import_aliases_cover_the_reference_paths():
@@ -48,32 +43,36 @@ def test_import_aliases_cover_the_reference_paths():
     assert r.returncode == 0 and "aliases ok" in r.stdout, r.stderr[-2000:]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_TESTS), reason="the reference tree only exists in the build container")
-def test_the_references_own_offline_tests_pass_against_this_build(tmp_path):
-    files = [os.path.join(REF_TESTS, f) for f in ("test_hooks.py", "test_cache_hook_names.py", "test_weight_properties.py",
-                                                   "sae/test_load_VisionModelSAERunnerConfig.py", "models/test_models.py")]
-    code = ("import sys, pytest, vit_prisma_amd\n"
-            "vit_prisma_amd.install_as('vit_prisma')\n"
-            f"sys.exit(pytest.main({files!r} + ['-q', '-p', 'no:cacheprovider']))\n")
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=str(tmp_path), env=env, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "22 passed" in r.stdout, r.stdout[-500:]
+_CKPT_CHECK = """
+import os, sys, torch
+from vit_prisma_amd.sae import StandardSparseAutoencoder, VisionModelSAERunnerConfig
+d = sys.argv[1]
+io = torch.load(os.path.join(d, "io.pt"))
+m = StandardSparseAutoencoder.load_from_pretrained(os.path.join(d, "ref_legacy.pt"))
+assert type(m.cfg) is VisionModelSAERunnerConfig and m.cfg.d_sae == 512 and m.cfg.activation_fn_kwargs == {"k": 8}
+assert torch.equal(m(io["x"])[0], io["out"])
+# split form: bare state dict + config.json beside it; the reference's positional order (weights_path, current_cfg)
+m2 = StandardSparseAutoencoder.load_from_pretrained(os.path.join(d, "weights.pt"), {"lr": 0.5, "not_a_field": 1})
+assert m2.cfg.lr == 0.5 and not hasattr(m2.cfg, "not_a_field") and torch.equal(m2(io["x"])[0], io["out"])
+m3 = StandardSparseAutoencoder.load_from_pretrained(os.path.join(d, "weights.pt"), config_path=os.path.join(d, "config.json"))
+assert torch.equal(m3(io["x"])[0], io["out"])
+try:
+    StandardSparseAutoencoder.load_from_pretrained(os.path.join(d, "nope.pt"))
+    raise SystemExit("no FileNotFoundError")
+except FileNotFoundError:
+    pass
+print("checkpoints ok")
+"""
 
 
 def test_checkpoints_written_by_the_reference_load_and_reproduce_its_output():
-    d = os.path.join(GOLDEN, "sae_ref_ckpt")
-    io = torch.load(os.path.join(d, "io.pt"))
-    m = StandardSparseAutoencoder.load_from_pretrained(os.path.join(d, "ref_legacy.pt"))
-    assert type(m.cfg) is VisionModelSAERunnerConfig and m.cfg.d_sae == 512 and m.cfg.activation_fn_kwargs == {"k": 8}
-    assert torch.equal(m(io["x"])[0], io["out"])
-    # split form: bare state dict + config.json beside it; the reference's positional order (weights_path, current_cfg)
-    m2 = StandardSparseAutoencoder.load_from_pretrained(os.path.join(d, "weights.pt"), {"lr": 0.5, "not_a_field": 1})
-    assert m2.cfg.lr == 0.5 and not hasattr(m2.cfg, "not_a_field") and torch.equal(m2(io["x"])[0], io["out"])
-    m3 = StandardSparseAutoencoder.load_from_pretrained(os.path.join(d, "weights.pt"), config_path=os.path.join(d, "config.json"))
-    assert torch.equal(m3(io["x"])[0], io["out"])
-    with pytest.raises(FileNotFoundError):
-        StandardSparseAutoencoder.load_from_pretrained(os.path.join(d, "nope.pt"))
+    """Bit for bit against the reference module's reconstruction (io.pt), which was computed with MKL's conditional numerical
+    reproducibility: the same setting here (in a fresh process: MKL reads it once) gives the same bits on any x86 CPU, where the
+    default code paths differ in the last bit between instruction sets."""
+    env = dict(os.environ, MKL_CBWR="COMPATIBLE", PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, "-c", _CKPT_CHECK, os.path.join(GOLDEN, "sae_ref_ckpt")], capture_output=True, text=True,
+                       cwd=ROOT, env=env, timeout=300)
+    assert r.returncode == 0 and "checkpoints ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 def test_geometric_median_equals_the_references():

@@ -1,17 +1,15 @@
 """real-weight conversion and the CLIP input transform.
 
-* ``convert_open_clip_weights`` / ``convert_hf_clip_weights`` against the REFERENCE's converters on a seeded synthetic
-  checkpoint (build container only; skipped where /root/reference is absent), and -- everywhere -- against an independent
+* ``convert_open_clip_weights`` / ``convert_hf_clip_weights`` against what the REFERENCE's converters returned on a seeded
+  synthetic checkpoint (tests/golden/weight_conversion_tiny.npz), and against an independent
   open_clip-style vision transformer written with torch's own ``multi_head_attention_forward``: HookedViT with the
   converted weights must reproduce its image embedding at atol 1e-4, the tolerance of the reference's own upstream-parity
   test (/root/reference/tests/test_loading_CLIP-ViT-B-32-DataComp-XL-s13B-b90K.py:14-111, which needs the network).
 * ``get_clip_val_transforms`` (PIL, the reference's pipeline) vs ``GpuClipTransform`` (batched, on device).
 """
 import os
-import sys
 
 import numpy as np
-import pytest
 import torch
 import torch.nn.functional as F
 
@@ -113,21 +111,22 @@ def test_converted_weights_reproduce_an_independent_open_clip_forward(tmp_path):
             assert torch.equal(m2.eval()(x), got)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="the reference tree only exists in the build container")
 def test_converters_equal_the_references_on_the_same_checkpoint():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    from _refimport import install
-    install()
-    from vit_prisma.models.weight_conversion import convert_open_clip_weights as ref_oc
-    from vit_prisma.models.weight_conversion import convert_kandinsky_clip_weights as ref_hf      # (its HF CLIPModel converter)
+    """Against what the reference's convert_open_clip_weights and its HF CLIPModel converter (convert_kandinsky_clip_weights)
+    returned for the seeded tiny checkpoint (tests/golden/weight_conversion_tiny.npz, gen_golden_weight_conversion.py)."""
+    z = np.load(os.path.join(ROOT, "tests", "golden", "weight_conversion_tiny.npz"))
+    part = lambda prefix: {k.split("::", 1)[1]: torch.from_numpy(z[k]) for k in z.files if k.startswith(prefix + "::")}  # noqa: E731
     cfg = tiny_cfg()
     sd = synth_open_clip_state(cfg, seed=3)
-    ours, ref = convert_open_clip_weights(sd, cfg), ref_oc(sd, cfg)
+    stored = part("in_open_clip")
+    assert set(stored) == set(sd) and all(torch.equal(sd[k], stored[k]) for k in sd)      # the checkpoint the reference converted
+    ours, ref = convert_open_clip_weights(sd, cfg), part("ref_open_clip")
     assert set(ours) == set(ref)
     for k in ref:
         assert ours[k].shape == ref[k].shape and torch.equal(ours[k], ref[k]), k
     hf_sd = to_hf_names(sd, cfg)
-    ours, ref = convert_hf_clip_weights(hf_sd, cfg), ref_hf(hf_sd, cfg, device="cpu")
+    ours, ref = convert_hf_clip_weights(hf_sd, cfg), part("ref_hf")
+    assert set(ref) <= set(ours)
     for k in ref:
         assert torch.equal(ours[k], ref[k]), k
 

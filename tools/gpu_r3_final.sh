@@ -5,7 +5,7 @@ cd $R
 timeout 2400 python -m pytest tests/ -m gpu -q > $O/tests_gpu.log 2>&1; echo "tests rc=$?" >> $O/tests_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log
 tail -4 $O/tests_gpu.log; tail -2 $O/smoke.log
-timeout 1200 python bench.py > $O/bench_full.json 2> $O/bench_full.err; echo "bench rc=$?"; tail -c 300 $O/bench_full.err
+timeout 1200 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err; echo "bench rc=$?"; tail -c 300 $O/bench_full.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_vit -o vit -- python $R/bench.py --no-sae --no-l14 --no-cpu-baseline --steps 10 --warmup 3 > $O/prof_vit_bench.json 2> $O/prof_vit.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sae -o sae -- python $R/tools/prof_sae.py > $O/prof_sae.out 2> $O/prof_sae.err

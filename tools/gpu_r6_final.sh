@@ -8,7 +8,7 @@ rm -f $R/gpurun_out/truncated_tests.txt
 timeout 2400 python -m pytest tests/ -m gpu -q -p no:cacheprovider --timeout=1500 --durations=8 > $O/tests_gpu.log 2>&1; echo "tests rc=$? $(( $(date +%s) - T0 ))s" >> $O/tests_gpu.log
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log
 grep -E "passed|failed|rc=" $O/tests_gpu.log | tail -4; grep -E "^FAILED|^ERROR" $O/tests_gpu.log | head; tail -2 $O/smoke.log
-timeout 900 python bench.py > $O/bench_full.json 2> $O/bench_full.err; echo "bench rc=$? $(( $(date +%s) - T0 ))s"; tail -c 300 $O/bench_full.err
+timeout 900 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err; echo "bench rc=$? $(( $(date +%s) - T0 ))s"; tail -c 300 $O/bench_full.err
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_vit -o vit -- python $R/bench.py --no-sae --no-l14 --no-cpu-baseline --steps 10 --warmup 3 > $O/prof_vit_bench.json 2> $O/prof_vit.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sae -o sae -- python $R/tools/prof_sae.py > $O/prof_sae.out 2> $O/prof_sae.err
