@@ -175,17 +175,18 @@ def test_cache_key_order_and_observe_only_points(model, x):
     assert model.hook_dict["blocks.1.mlp.hook_post"].layer() == 1
 
 
-def test_boundary_hook_classification_for_the_split_native_plan(model, x):
-    """Which registered hooks the HIP plan can serve by splitting (HookedViT._boundary_hooks): forward hooks on the
+def test_hook_sites_classify_hooks_for_the_split_native_plan(model, x):
+    """Which registered hooks the HIP plan can serve by splitting (HookedViT._boundary_hooks, split_plan.hook_sites): forward hooks on the
     residual-stream points of a block -- hook_resid_pre (block >= 1), hook_attn_out, hook_resid_mid, hook_mlp_out,
     hook_resid_post -- and on every point inside it: ln1 / ln2 .hook_scale / .hook_normalized, attn.hook_q / hook_k / hook_v,
     attn.hook_attn_scores, attn.hook_pattern, attn.hook_z, mlp.hook_pre, mlp.hook_post, keyed by position (ten per block: entry |
     ln1 | q, k, v | scores | pattern | z | after the attention half | ln2 | mlp pre | mlp post); hooks on the embedding stage (incl.
-    block 0's resid_pre) and on the final stage are classified under two special keys -- those stages then run on the model's own
-    modules and the blocks stay on the plan; anything else (the flag-gated points, backward hooks) keeps the PyTorch path.  On CPU the
+    block 0's resid_pre) and on the final stage are classified apart -- those stages then run on the model's own modules and the
+    blocks stay on the plan; anything else (backward hooks, points the plan cannot be split at) keeps the PyTorch path.  On CPU the
     call itself always runs in PyTorch."""
+    from vit_prisma_amd.split_plan import LN2, MID, NPOS, HookSites
     ident = lambda t, hook: t  # noqa: E731
-    assert model._boundary_hooks() == {}
+    assert model._boundary_hooks() == HookSites()
     with model.hooks(fwd_hooks=[("blocks.0.hook_resid_post", ident), ("blocks.1.hook_resid_pre", ident),
                                 ("blocks.1.hook_resid_post", ident), ("blocks.0.hook_mlp_out", ident),
                                 ("blocks.1.hook_attn_out", ident), ("blocks.0.hook_resid_mid", ident),
@@ -194,7 +195,9 @@ def test_boundary_hook_classification_for_the_split_native_plan(model, x):
                                 ("blocks.1.attn.hook_attn_scores", ident), ("blocks.0.ln2.hook_scale", ident),
                                 ("blocks.1.mlp.hook_pre", ident), ("blocks.1.ln1.hook_normalized", ident),
                                 ("blocks.1.ln1.hook_scale", ident)]):
-        bh = model._boundary_hooks()
+        sites = model._boundary_hooks()
+        bh = sites.at
+        assert sites == HookSites(at=bh)                  # nothing on the embedding / final stage, no block on module code
         assert sorted(bh) == [4, 5, 6, 7, 10, 11, 12, 13, 16, 18, 19, 20]
         assert sorted(bh[4]) == ["pattern"] and sorted(bh[5]) == ["z"] and sorted(bh[6]) == ["mid"] and sorted(bh[7]) == ["ln2s"]
         assert sorted(bh[10]) == ["mlp", "post", "pre"] and sorted(bh[11]) == ["ln1n", "ln1s"] and sorted(bh[12]) == ["q", "v"]
@@ -203,25 +206,33 @@ def test_boundary_hook_classification_for_the_split_native_plan(model, x):
         assert bh[10]["post"] is model.hook_dict["blocks.0.hook_resid_post"]
         out = model(x)                                   # CPU input: PyTorch path, result defined by the hooks
         assert out.shape[0] == B and not model.last_run_native
-    assert model._boundary_hooks() == {}
-    for name, key in (("blocks.0.hook_resid_pre", model._EMBED_POS), ("hook_embed", model._EMBED_POS), ("hook_pos_embed", model._EMBED_POS),
-                      ("ln_final.hook_normalized", model._FINAL_POS), ("hook_ln_final", model._FINAL_POS)):
+    assert model._boundary_hooks() == HookSites()
+    for name, key in (("blocks.0.hook_resid_pre", "embed"), ("hook_embed", "embed"), ("hook_pos_embed", "embed"),
+                      ("ln_final.hook_normalized", "final"), ("hook_ln_final", "final")):
         with model.hooks(fwd_hooks=[(name, ident)]):
-            assert list(model._boundary_hooks()) == [key], name
+            assert model._boundary_hooks() == HookSites(**{key: {name: model.hook_dict[name]}}), name
     for name, flag in (("blocks.0.hook_mlp_in", "use_hook_mlp_in"), ("blocks.1.attn.hook_result", "use_attn_result"),
                        ("blocks.0.hook_q_input", "use_split_qkv_input")):
         with model.hooks(fwd_hooks=[(name, ident)]):
-            assert model._boundary_hooks() == {}, name                  # flag off: the point is never called, the hook cannot fire
-            setattr(model.cfg, flag, True)                              # flag on (round 6): served ON the plan -- hook_mlp_in / hook_result as kinds
-            try:                                                        # of their own at the block's positions 7 / 6, the per-head inputs by _head_glue
-                l, hp = int(name.split(".")[1]), model.hook_dict[name]
-                want = {"use_hook_mlp_in": {model._NPOS * l + 7: {"mlpin": hp}}, "use_attn_result": {model._NPOS * l + 6: {"result": hp}},
-                        "use_split_qkv_input": {model._HEAD_POS: {l: True}}}[flag]
+            assert model._boundary_hooks() == HookSites(), name                 # flag off: the point is never called, the hook cannot fire
+            setattr(model.cfg, flag, True)                              # flag on: served ON the plan -- hook_mlp_in / hook_result as kinds
+            try:                                                        # of their own at the block's positions 7 / 6, the per-head inputs by
+                l, hp = int(name.split(".")[1]), model.hook_dict[name]  # running only the block's head on module code
+                want = {"use_hook_mlp_in": HookSites(at={NPOS * l + LN2: {"mlpin": hp}}),
+                        "use_attn_result": HookSites(at={NPOS * l + MID: {"result": hp}}),
+                        "use_split_qkv_input": HookSites(head_blocks={l})}[flag]
                 assert model._boundary_hooks() == want, name
             finally:
                 setattr(model.cfg, flag, False)
     with model.hooks(bwd_hooks=[("blocks.0.hook_resid_post", ident)]):
         assert model._boundary_hooks() is None
+    norm = model.cfg.normalization_type
+    with model.hooks(fwd_hooks=[("blocks.1.ln2.hook_scale", ident)]):
+        model.cfg.normalization_type = None                         # (a point the plan cannot be split at)
+        try:
+            assert model._boundary_hooks() is None
+        finally:
+            model.cfg.normalization_type = norm
 
 
 def test_spliced_modules_disable_the_native_plan(model, x):

@@ -1,4 +1,4 @@
-"""The split native plan of HookedViT._run_with_cache_native (ten positions per block, hooks applied between segments, forced taps,
+"""The split native plan of vit_prisma_amd/split_plan.py (ten positions per block, hooks applied between segments, forced taps,
 carried residual stream and activations) on CPU: the HIP backend is replaced by a stand-in that computes a SEGMENT
 (first_block / entry_stage .. n_blocks / exit_stage, requested taps) with plain torch arithmetic on the model's own parameters and
 never touches a HookPoint -- so everything the orchestration gets wrong (a hook applied twice or not at all, a wrong resume
@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from vit_prisma_amd import HookedViT, HookedViTConfig
+from vit_prisma_amd.split_plan import HookSites
 
 B, S, P = 3, 32, 8
 
@@ -31,8 +32,8 @@ class SegmentBackend:
         self.calls = []
 
     def forward(self, model, images, names, n_blocks, run_head, cache_device=None, remove_batch_dim=False, first_block=0,
-                resid_in=None, entry_mid=False, exit_mid=False, entry_stage=0, exit_stage=0, act_in=()):
-        es, xs = (6 if entry_mid else entry_stage), (6 if exit_mid else exit_stage)
+                resid_in=None, entry_stage=0, exit_stage=0, act_in=()):
+        es, xs = entry_stage, exit_stage
         self.calls.append((first_block, es, n_blocks, xs, bool(run_head)))
         want, taps, cfg, m = set(names), {}, model.cfg, model
 
@@ -395,6 +396,10 @@ def test_flag_gated_points_are_derived_from_the_plan(flags):
     if F_.get("use_hook_mlp_in"):
         mixed.append([("blocks.1.hook_mlp_in", scale_shift), ("blocks.1.hook_mlp_out", half), ("blocks.2.hook_resid_pre", half),
                       ("ln_final.hook_normalized", half)])
+        # LayerNorm 2 normalises what hook_mlp_in returns, also where its own points are hooked
+        mixed.append([("blocks.1.hook_mlp_in", scale_shift), ("blocks.1.ln2.hook_scale", lambda t, hook: None)])
+        mixed.append([("blocks.1.hook_mlp_in", scale_shift), ("blocks.1.ln2.hook_scale", half)])
+        mixed.append([("blocks.1.hook_mlp_in", scale_shift), ("blocks.1.ln2.hook_normalized", half)])
     if F_.get("use_attn_in") or F_.get("use_split_qkv_input"):
         mixed.append([("blocks.1.ln1.hook_scale", freeze_scale), ("blocks.0.ln2.hook_normalized", half)])
     with torch.no_grad():
@@ -467,7 +472,7 @@ SPLICES = [["blocks.0.hook_resid_post"], ["blocks.1.hook_mlp_out", "blocks.2.hoo
 
 
 @pytest.mark.parametrize("case", range(len(SPLICES)))
-def test_spliced_modules_are_served_by_the_plan(case):
+def test_spliced_modules_are_served_by_the_split_plan(case):
     model = _make_sae_model()
     x = torch.rand(B, 3, S, S, generator=torch.Generator().manual_seed(1))
     d_of = lambda name: 8 if name.endswith("hook_z") else 16  # noqa: E731
@@ -497,12 +502,13 @@ def test_spliced_modules_are_served_by_the_plan(case):
     # a splice the plan cannot serve at a block's point (a LayerNorm point, block 0's entry): that block on its own module; on the
     # embedding / final stage: that stage on the model's own modules (as for a hook there), every block on the plan
     model.reset_saes()
-    assert model._tree_matches() and model._boundary_hooks() == {}
+    assert model._tree_matches() and model._boundary_hooks() == HookSites()
     with torch.no_grad():
-        for name, key in (("blocks.1.ln2.hook_normalized", model._TORCH_POS), ("blocks.0.hook_resid_pre", model._TORCH_POS),
-                          ("hook_embed", model._EMBED_POS), ("hook_post_head_pre_normalize", model._FINAL_POS)):
-            model.add_sae(_ToySAE(5 if name.startswith("hook_post") else 16, name, seed=5))
-            assert model._tree_matches() and list(model._boundary_hooks()) == [key], name
+        for name, key in (("blocks.1.ln2.hook_normalized", "module_blocks"), ("blocks.0.hook_resid_pre", "module_blocks"),
+                          ("hook_embed", "embed"), ("hook_post_head_pre_normalize", "final")):
+            model.add_sae(sae := _ToySAE(5 if name.startswith("hook_post") else 16, name, seed=5))
+            want = HookSites(**{key: {int(name.split(".")[1])} if key == "module_blocks" else {name: sae}})
+            assert model._tree_matches() and model._boundary_hooks() == want, name
             for kw in FORMS:
                 model.use_native(False)
                 w_out, w_cache = model.run_with_cache(x.clone(), **kw)

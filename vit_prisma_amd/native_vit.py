@@ -267,8 +267,7 @@ class NativeViT:
 
     def forward(self, model, images: Optional[torch.Tensor], names: Sequence[str], n_blocks: int, run_head: bool,
                 cache_device=None, remove_batch_dim: bool = False, first_block: int = 0,
-                resid_in: Optional[torch.Tensor] = None, entry_mid: bool = False,
-                exit_mid: bool = False, entry_stage: int = 0, exit_stage: int = 0,
+                resid_in: Optional[torch.Tensor] = None, entry_stage: int = 0, exit_stage: int = 0,
                 act_in: Sequence[torch.Tensor] = (),
                 tap_dst: Optional[Dict[str, torch.Tensor]] = None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
         """Runs the tapped forward.  ``names``: requested HookPoint names in firing order.
@@ -279,14 +278,13 @@ class NativeViT:
         With ``resid_in`` ([B, T, d_model]) the forward is RESUMED at block ``first_block`` from that residual
         (``images`` is ignored, names of earlier stages must not be requested).  Positions inside a block
         (``entry_stage`` / ``exit_stage``, pv_vit_forward_stage; PV_STAGE_*): 0 block entry, 1 ln1 taken, 2 q / k / v ready,
-        3 attention scores, 4 pattern, 5 z ready, 6 after the attention half (``entry_mid`` / ``exit_mid`` = 6), 7 ln2 taken,
+        3 attention scores, 4 pattern, 5 z ready, 6 after the attention half, 7 ln2 taken,
         8 mlp pre ready, 9 mlp post ready.  A segment that exits at a stage runs block ``n_blocks`` up to it; one that enters at a
         stage gets the residual stream the rest of the block adds to in ``resid_in`` and the (hook-edited) activations of the stage
         in ``act_in``: (normalized fp32,) | (q, k, v) | (scores, v) | (pattern, v) | (z,) | (normalized fp32,) | (pre,) | (post,).
         Returns (model_out, {name: tensor}); for an exit inside the attention half or the MLP model_out is the stage's (first)
         activation."""
-        entry_stage = 6 if entry_mid else int(entry_stage)
-        exit_stage = 6 if exit_mid else int(exit_stage)
+        entry_stage, exit_stage = int(entry_stage), int(exit_stage)
         cfg = self.cfg
         T = self.n_tokens
         if resid_in is not None:

@@ -12,7 +12,7 @@ semantics identical; state dicts interchange):
     HookedViT         models/base_vit.py:60-269, 670-824
 
 ``HookedViT.run_with_cache`` dispatches pure-caching calls on a GPU to the native HIP plan
-(``native_vit.NativeViT`` -> libpvnative.so); every module's ``forward`` below is the faithful
+(``split_plan.run`` -> ``native_vit.NativeViT`` -> libpvnative.so; split at hooked points); every module's ``forward`` below is the faithful
 PyTorch implementation used when user hooks must run as Python callbacks (mutating hooks,
 backward hooks, per-head input hooks, training mode) and on machines without a GPU.
 """
@@ -21,20 +21,17 @@ from __future__ import annotations
 import logging
 
 import math
-from typing import Dict, List, Optional, Tuple, Union
-
-import re
+from typing import Dict, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _native
+from . import _native, split_plan
 from .activation_cache import ActivationCache
 from .configs import HookedViTConfig
 from .hook_points import HookPoint
-from .hooked_root_module import HookedRootModule, names_filter_to_fn
-from .tap_plan import FLAG_POINTS, hook_order, resolve_n_blocks
+from .hooked_root_module import HookedRootModule
 
 
 def _as_cfg(cfg: Union[Dict, HookedViTConfig]) -> HookedViTConfig:
@@ -335,11 +332,11 @@ class HookedViT(HookedRootModule):
             if not getattr(self, "_in_cache_fallback", False):
                 reason = self._native_reason((input,), {"stop_at_layer": stop_at_layer})
                 if reason is None:
-                    out, _ = self._run_with_cache_native(input, False, names_filter=[], stop_at_layer=stop_at_layer)
+                    out, _ = split_plan.run(self, input, names_filter=[], stop_at_layer=stop_at_layer)
                     self.last_run_native = True
                     self.native_fallback_reason = None
                     return out
-                if self.native_mode == "force" and self._boundary_hooks() != {}:
+                if self.native_mode == "force" and self._boundary_hooks() != split_plan.HookSites():
                     raise _native.NativeError(f"native forward with hooks impossible: {reason}")
                 self.last_run_native = False
                 self.native_fallback_reason = reason
@@ -475,41 +472,6 @@ class HookedViT(HookedRootModule):
                 return "nn.Module hooks registered"
         return None
 
-    # HookPoints a forward hook may sit on while the call stays on the native plan: the plan is split there
-    _BOUNDARY_RE = re.compile(r"blocks\.(\d+)\.(hook_resid_pre|hook_attn_out|hook_resid_mid|hook_mlp_out|hook_resid_post|"
-                              r"ln1\.hook_scale|ln1\.hook_normalized|ln2\.hook_scale|ln2\.hook_normalized|"
-                              r"attn\.hook_q|attn\.hook_k|attn\.hook_v|attn\.hook_attn_scores|attn\.hook_pattern|attn\.hook_z|"
-                              r"mlp\.hook_pre|mlp\.hook_post)$")
-    # split positions per block (= PV_STAGE_*): 0 entry | 1 ln1 taken | 2 q, k, v ready | 3 scores | 4 pattern | 5 z ready | 6 after the
-    # attention half | 7 ln2 taken | 8 mlp pre ready | 9 mlp post ready
-    _NPOS = 10
-    # hooks on the embedding stage / the final stage: those two stages then run on the model's own PyTorch modules (a conv, a
-    # LayerNorm, a [B, d] x [d, n_classes] product -- under 1 % of the forward), their HookPoints firing as usual, and every block
-    # stays on the HIP plan, resumed from / stopped at the residual stream (special keys of _boundary_hooks())
-    _EMBED_POS, _FINAL_POS = -1, 1 << 30
-    # blocks that must run on their own PyTorch module (special key of _boundary_hooks(): {block index: True}): a forward hook on one
-    # of the block's flag-gated points (hook_attn_in, hook_q_input / k / v, attn.hook_result, hook_mlp_in) or on ln1 while the block
-    # inputs carry a head dimension, a module spliced on one of its LayerNorm points or on block 0's entry.  Every HookPoint of such a
-    # block fires inside its module's forward; the blocks around it stay on the HIP plan.
-    _TORCH_POS = -2
-    # round 6: hooks ON flag-gated points no longer send the block to PyTorch.  attn.hook_result and hook_mlp_in are kinds of their own
-    # at the block's positions 6 / 7 ("result": z against W_O per head in one einsum, the hook, the head sum folded back -- attention.py:
-    # 155-183; "mlpin": the hook on a copy of resid_mid, ln2 of what it returns as the module computes it -- transformer_block.py:125-129);
-    # hooks on the per-head block inputs (hook_attn_in, hook_q_input / k / v, or ln1 while the inputs carry a head dimension) put the
-    # block under _HEAD_POS: ITS head -- per-head inputs, per-head ln1, per-head q / k / v projections -- runs on the module's own code
-    # (_head_glue: that is where those HookPoints live), everything behind q / k / v (attention core, O-projection, LayerNorm 2, the
-    # MLP: 3/4 of the block's FLOP) stays on the HIP plan, entered at PV_STAGE_QKV.
-    _HEAD_POS = -3
-    _FLAG_RE = re.compile(r"blocks\.(\d+)\.(hook_attn_in|hook_q_input|hook_k_input|hook_v_input|attn\.hook_result|hook_mlp_in)$")
-    _EMBED_NAMES = ("hook_embed", "hook_pos_embed", "hook_full_embed", "ln_pre.hook_scale", "ln_pre.hook_normalized", "hook_ln_pre")
-    _FINAL_NAMES = ("ln_final.hook_scale", "ln_final.hook_normalized", "hook_ln_final", "hook_post_head_pre_normalize")
-    _KIND_POS = {"hook_resid_pre": ("pre", 0), "ln1.hook_scale": ("ln1s", 1), "ln1.hook_normalized": ("ln1n", 1),
-                 "attn.hook_q": ("q", 2), "attn.hook_k": ("k", 2), "attn.hook_v": ("v", 2),
-                 "attn.hook_attn_scores": ("scores", 3), "attn.hook_pattern": ("pattern", 4),
-                 "attn.hook_z": ("z", 5), "hook_attn_out": ("attn", 6), "hook_resid_mid": ("mid", 6),
-                 "ln2.hook_scale": ("ln2s", 7), "ln2.hook_normalized": ("ln2n", 7), "mlp.hook_pre": ("mlppre", 8),
-                 "mlp.hook_post": ("mlppost", 9), "hook_mlp_out": ("mlp", 10), "hook_resid_post": ("post", 10)}
-
     def _spliced(self) -> Dict[str, nn.Module]:
         """{hook point name: module standing in its place} -- the SAEs HookedSAEViT.add_sae spliced in (empty otherwise)"""
         return getattr(self, "acts_to_saes", None) or {}
@@ -532,84 +494,16 @@ class HookedViT(HookedRootModule):
                     return False
         return True
 
-    def _boundary_hooks(self) -> Optional[Dict[int, Dict[str, HookPoint]]]:
-        """{position: {kind: HookPoint}} for every HookPoint that carries a forward hook, or None when some hook (a
-        forward hook elsewhere, any backward hook) cannot be served by splitting the native plan.  Positions count
-        _NPOS = 10 per block: 10b = the residual stream entering block b (kinds "mlp", "post" of block b-1 and "pre" of block b
-        fire there, in that order), +1 = its ln1 ("ln1s", then "ln1n"), +2 = its q, k, v, +3 = its attention scores, +4 = its
-        pattern, +5 = its z, +6 = after its attention half ("attn", then "mid"), +7 = its ln2, +8 = its MLP pre-activation,
-        +9 = its MLP activation."""
-        out: Dict[int, Dict[str, HookPoint]] = {}
-        spliced = self._spliced()
-        for name, mod in spliced.items():
-            # a module spliced in place of a block's HookPoint: called on the tapped tensor like the HookPoint's hooks would be
-            # (it returns what the block continues from: an SAE with cfg.return_out_only).  Elsewhere, or in another dtype than
-            # the plan's: the PyTorch path.
-            m = self._BOUNDARY_RE.fullmatch(name)
-            if getattr(mod, "dtype", self.cfg.dtype) != self.cfg.dtype:
-                return None
-            if m is None:
-                # on the embedding / final stage: that stage runs on the model's own modules anyway when it is hooked, and the
-                # spliced module is then simply what the stage calls
-                if name in self._EMBED_NAMES:
-                    out.setdefault(self._EMBED_POS, {})[name] = mod
-                elif name in self._FINAL_NAMES:
-                    out.setdefault(self._FINAL_POS, {})[name] = mod
-                else:
-                    return None
-                continue
-            kind, off = self._KIND_POS[m.group(2)]
-            pos = self._NPOS * int(m.group(1)) + off
-            # (a splice on the tensor a flag-gated point is derived from -- the block input under use_attn_in / use_split_qkv_input,
-            # z under use_attn_result, resid_mid under use_hook_mlp_in: that point then sees the MODULE's output, which no tap holds;
-            # the block runs on its own module and records its flag-gated points itself)
-            feeds_flag_point = {"pre": self.cfg.use_attn_in or self.cfg.use_split_qkv_input, "z": self.cfg.use_attn_result,
-                                "mid": self.cfg.use_hook_mlp_in}.get(kind, False)
-            if pos == 0 or kind.startswith("ln") or feeds_flag_point:
-                out.setdefault(self._TORCH_POS, {})[int(m.group(1))] = True
-                continue
-            out.setdefault(pos, {})[kind] = mod
-        for name, hp in self.hook_dict.items():
-            if hp._backward_hooks:
-                return None
-            if not hp._forward_hooks:
-                continue
-            if spliced and any(name.startswith(x + ".") for x in spliced):
-                continue                                          # a spliced module's own HookPoints fire inside its forward
-            if name in self._EMBED_NAMES:
-                out.setdefault(self._EMBED_POS, {})[name] = hp
-                continue
-            if name in self._FINAL_NAMES:
-                out.setdefault(self._FINAL_POS, {})[name] = hp
-                continue
-            m = self._BOUNDARY_RE.fullmatch(name)
-            if m is None:
-                f = self._FLAG_RE.fullmatch(name)
-                if f is None:
-                    return None
-                flag = {"hook_attn_in": "use_attn_in", "attn.hook_result": "use_attn_result", "hook_mlp_in": "use_hook_mlp_in"}.get(
-                    f.group(2), "use_split_qkv_input")
-                if getattr(self.cfg, flag):                       # (with its flag off the point is never called: the hook cannot fire)
-                    l_ = int(f.group(1))
-                    if f.group(2) == "attn.hook_result":
-                        out.setdefault(self._NPOS * l_ + 6, {})["result"] = hp
-                    elif f.group(2) == "hook_mlp_in":
-                        out.setdefault(self._NPOS * l_ + 7, {})["mlpin"] = hp
-                    else:
-                        out.setdefault(self._HEAD_POS, {})[l_] = True
-                continue
-            kind, off = self._KIND_POS[m.group(2)]
-            if kind.startswith("ln") and self.cfg.normalization_type not in ("LN", "LNPre"):
-                return None
-            if kind.startswith("ln1") and (self.cfg.use_attn_in or self.cfg.use_split_qkv_input):
-                out.setdefault(self._HEAD_POS, {})[int(m.group(1))] = True      # (ln1's HookPoints carry a head dimension there: _head_glue)
-                continue
-            pos = self._NPOS * int(m.group(1)) + off
-            if pos == 0:
-                out.setdefault(self._EMBED_POS, {})[name] = hp      # blocks.0.hook_resid_pre is the embedding stage's last tensor
-                continue
-            out.setdefault(pos, {})[kind] = hp
-        return out
+    def _boundary_hooks(self) -> Optional[split_plan.HookSites]:
+        """Where the forward hooks and spliced modules sit for the split native plan; None: some hook cannot be served."""
+        return split_plan.hook_sites(self)
+
+    def _torch_block_stage(self, l: int, resid: torch.Tensor, wanted) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+        """Block l on its own module, its HookPoints firing inside: (its output, {name: tensor} of its points in `wanted`)."""
+        rec: Dict[str, torch.Tensor] = {}
+        with split_plan.recording(self, [n for n in self.hook_dict if n.startswith(f"blocks.{l}.") and n in wanted], rec):
+            out = self.blocks[l](resid)
+        return out.contiguous(), rec
 
     def _get_native(self, device: torch.device):
         from .native_vit import NativeViT
@@ -636,11 +530,11 @@ class HookedViT(HookedRootModule):
                             clear_contexts=kwargs.get("clear_contexts", False)):
                 reason = self._native_reason(model_args, kwargs)
                 if reason is None:
-                    out, cache_dict = self._run_with_cache_native(model_args[0], remove_batch_dim, **kwargs)
+                    out, cache_dict = split_plan.run(self, model_args[0], remove_batch_dim=remove_batch_dim, **kwargs)
         else:
             reason = self._native_reason(model_args, kwargs)
             if reason is None:
-                out, cache_dict = self._run_with_cache_native(model_args[0], remove_batch_dim, **kwargs)
+                out, cache_dict = split_plan.run(self, model_args[0], remove_batch_dim=remove_batch_dim, **kwargs)
         if reason is None:
             self.last_run_native = True
             self.native_fallback_reason = None
@@ -658,544 +552,6 @@ class HookedViT(HookedRootModule):
         if return_cache_object:
             return out, ActivationCache(cache_dict, self, has_batch_dim=not remove_batch_dim)
         return out, cache_dict
-
-    def _run_with_cache_native(self, x: torch.Tensor, remove_batch_dim: bool, names_filter=None, device=None,
-                               stop_at_layer: Optional[int] = None, **_ignored):
-        """The caching run on the HIP plan.  With flag-gated HookPoints enabled (cfg.use_attn_in / use_split_qkv_input /
-        use_attn_result / use_hook_mlp_in) the plan runs as always -- without a hook on them those points do not change the forward
-        -- and their cache entries are derived afterwards from what the plan tapped (transformer_block.py:88-129,
-        attention.py:155-183): hook_attn_in / hook_q_input / k / v = the block input with a head dimension (a stride-0 view: the
-        reference materialises H copies), ln1's two points carry that head dimension too, attn.hook_result = z against W_O per head
-        (one einsum per layer), hook_mlp_in = a copy of hook_resid_mid.  The head-dimension entries are stride-0 ``expand`` views of the
-        tensor they come from (the reference holds H copies: 12x the bytes at B/32): an in-place write into one raises torch's
-        overlapping-memory error instead of silently reaching its siblings -- ``.clone()`` it first.  A forward hook ON such a point changes that block's forward: the block
-        runs on its own PyTorch module (_run_blocks_mixed), the others stay on the plan."""
-        cfg = self.cfg
-        if not (cfg.use_attn_in or cfg.use_split_qkv_input or cfg.use_attn_result or cfg.use_hook_mlp_in):
-            return self._run_with_cache_plan(x, remove_batch_dim, names_filter, device, stop_at_layer)
-        keep = names_filter_to_fn(names_filter)
-        run_head = stop_at_layer is None
-        n_blocks = cfg.n_layers if run_head else resolve_n_blocks(cfg.n_layers, stop_at_layer)
-        # (modules spliced in place of HookPoints: their own HookPoints stand where the replaced point stood, as in _run_with_cache_plan)
-        spliced = self._spliced()
-        expanded: List[str] = []
-        for n in hook_order(cfg, n_blocks, run_head):
-            expanded += [k for k in self.hook_dict if k.startswith(n + ".")] if n in spliced else [n]
-        wanted = [n for n in expanded if keep(n)]
-        source = {"hook_attn_in": "hook_resid_pre", "hook_q_input": "hook_resid_pre", "hook_k_input": "hook_resid_pre",
-                  "hook_v_input": "hook_resid_pre", "attn.hook_result": "attn.hook_z", "hook_mlp_in": "hook_resid_mid"}
-
-        def split(name: str):
-            """("blocks.L.", rest) of a block's point, ("", name) otherwise"""
-            if name.startswith("blocks."):
-                _, l, rest = name.split(".", 2)
-                return f"blocks.{l}.", rest
-            return "", name
-
-        need = set(wanted)                                       # (a block that runs on its own module records its flag-gated points itself)
-        for n in wanted:
-            pre, rest = split(n)
-            if rest in FLAG_POINTS:
-                need.add(pre + source[rest])
-        out, got = self._run_with_cache_plan(x, False, lambda n: n in need, None, stop_at_layer)
-        H = cfg.n_heads
-        headed = cfg.use_attn_in or cfg.use_split_qkv_input
-        cache: Dict[str, torch.Tensor] = {}
-        for n in wanted:
-            pre, rest = split(n)
-            if n in got and rest in FLAG_POINTS:
-                t = got[n]
-            elif rest in FLAG_POINTS:
-                src = got.get(pre + source[rest])
-                if src is None:
-                    continue                                      # (behind stop_at_layer)
-                if rest == "attn.hook_result":
-                    t = torch.einsum("bphd,hdm->bphm", src, self.blocks[int(pre.split(".")[1])].attn.W_O)
-                elif rest == "hook_mlp_in":
-                    t = src.clone()                               # (its own storage, like the reference's: an in-place edit of one entry must not reach hook_resid_mid)
-                else:
-                    t = src.unsqueeze(2).expand(-1, -1, H, -1)
-            elif n not in got:
-                continue                                          # (a spliced module behind stop_at_layer never ran)
-            elif headed and rest in ("ln1.hook_scale", "ln1.hook_normalized") and got[n].ndim == 3:
-                t = got[n].unsqueeze(2).expand(-1, -1, H, -1)
-            else:
-                t = got[n]
-            if device is not None:
-                t = t.to(device)
-            cache[n] = t[0] if remove_batch_dim else t
-        return out, cache
-
-    def _run_with_cache_plan(self, x: torch.Tensor, remove_batch_dim: bool, names_filter=None, device=None,
-                             stop_at_layer: Optional[int] = None):
-        """The plan's own points; with modules spliced in place of HookPoints (HookedSAEViT) their own HookPoints
-        (``<point>.hook_sae_in`` ...) take the replaced point's place in the cache, recorded while the module runs."""
-        spliced = self._spliced()
-        if not spliced:
-            return self._run_with_cache_core(x, remove_batch_dim, names_filter, device, stop_at_layer)
-        cfg = self.cfg
-        keep = names_filter_to_fn(names_filter)
-        run_head = stop_at_layer is None
-        n_blocks = cfg.n_layers if run_head else resolve_n_blocks(cfg.n_layers, stop_at_layer)
-        expanded: List[str] = []
-        for n in hook_order(cfg, n_blocks, run_head):
-            expanded += [k for k in self.hook_dict if k.startswith(n + ".")] if n in spliced else [n]
-        wanted = [n for n in expanded if keep(n)]
-        inner = [n for n in wanted if any(n.startswith(x_ + ".") for x_ in spliced)]
-        plan_names = [n for n in wanted if n not in inner]
-        rec: Dict[str, torch.Tensor] = {}
-        added = []
-        for n in inner:                                          # (HookPoint-level hooks: the module then runs its hookable forward)
-            hp = self.hook_dict[n]
-            hp.add_hook(lambda t, hook, n=n: rec.__setitem__(n, t.detach()))
-            added.append((hp, hp.fwd_hooks[-1]))
-        try:
-            out, got = self._run_with_cache_core(x, False, plan_names, None, stop_at_layer)
-        finally:
-            for hp, h in added:
-                h.hook.remove()
-                hp.fwd_hooks.remove(h)
-        cache: Dict[str, torch.Tensor] = {}
-        for n in wanted:
-            t = rec.get(n) if n in rec else got.get(n)
-            if t is None:
-                continue                                          # (a spliced module behind stop_at_layer never ran)
-            if device is not None:
-                t = t.to(device)
-            cache[n] = t[0] if remove_batch_dim else t
-        return out, cache
-
-    def _run_with_cache_core(self, x: torch.Tensor, remove_batch_dim: bool, names_filter=None, device=None,
-                             stop_at_layer: Optional[int] = None):
-        cfg = self.cfg
-        keep = names_filter_to_fn(names_filter)
-        run_head = stop_at_layer is None
-        n_blocks = cfg.n_layers if run_head else resolve_n_blocks(cfg.n_layers, stop_at_layer)
-        names = [n for n in hook_order(cfg, n_blocks, run_head) if keep(n)]
-        bh = dict(self._boundary_hooks() or {})
-        # (flag-gated points are no taps of the plan: a HOOKED attn.hook_result / hook_mlp_in is produced -- and recorded -- where its
-        # hook is served, the per-head block inputs by _head_glue; the unhooked ones are derived by the caller)
-        served = {f"blocks.{q // self._NPOS}." + ("attn.hook_result" if k_ == "result" else "hook_mlp_in")
-                  for q, kinds in bh.items() if q >= 0 for k_ in kinds if k_ in ("result", "mlpin")}
-        on_plan = [n for n in names if self._FLAG_RE.fullmatch(n) is None or n in served]
-        embed_hooked = bh.pop(self._EMBED_POS, None) is not None
-        final_hooked = (bh.pop(self._FINAL_POS, None) is not None) and run_head
-        hblocks = set(l for l in (bh.pop(self._HEAD_POS, None) or {}) if l < n_blocks)
-        tblocks = sorted(set(l for l in (bh.pop(self._TORCH_POS, None) or {}) if l < n_blocks) | hblocks)
-        hblocks -= set(l for l in (self._boundary_hooks() or {}).get(self._TORCH_POS, {}))      # (a block that needs its module anyway)
-        if not embed_hooked and not final_hooked and not tblocks:
-            return self._run_native_segments(x, None, on_plan, n_blocks, run_head, bh, device, remove_batch_dim)
-        # hooks on the embedding / final stage, blocks that need their own module: those on PyTorch (their hooks fire as usual),
-        # every other block on the HIP plan
-        wanted = set(names)
-        cache: Dict[str, torch.Tensor] = {}
-        start = None
-        if embed_hooked:
-            # (block 0's hook_resid_pre belongs to the embedding stage's tail -- unless block 0 runs on its module, which fires it)
-            start, rec = self._torch_embedding_stage(x, wanted, 0 if (tblocks and tblocks[0] == 0) else n_blocks)
-            cache.update(rec)
-        inner = [n for n in on_plan if n not in cache and not (final_hooked and n in self._FINAL_NAMES)
-                 and not (embed_hooked and (n in self._EMBED_NAMES or n == "blocks.0.hook_resid_pre"))]
-        head_on_plan = run_head and not final_hooked
-        if tblocks:
-            out = self._run_blocks_mixed(x, start, inner, n_blocks, head_on_plan, bh, tblocks, cache, wanted, hblocks)
-        elif n_blocks > 0 or head_on_plan or start is None:
-            out, c = self._run_native_segments(x, start, inner, n_blocks, head_on_plan, bh, None, False)
-            cache.update(c)
-        else:
-            out = start                                          # stop_at_layer = 0 behind a hooked embedding stage
-        if final_hooked:
-            out, rec = self._torch_final_stage(out, wanted)
-            cache.update(rec)
-        ordered: Dict[str, torch.Tensor] = {}
-        for n in names:
-            if n not in cache:
-                continue                                          # (a flag-gated point of a block on the plan: derived by the caller)
-            t = cache[n]
-            if device is not None:
-                t = t.to(device)
-            ordered[n] = t[0] if remove_batch_dim else t
-        return out, ordered
-
-    def _run_blocks_mixed(self, x, start, names, n_blocks: int, run_head: bool, bh, tblocks, cache, wanted, hblocks=frozenset()):
-        """Blocks 0 .. n_blocks - 1 (+ the head) where the blocks of `tblocks` run on their own PyTorch module (every HookPoint of
-        such a block fires inside it: transformer_block.py:80-138) and the runs of blocks between them on the HIP plan, resumed from
-        / stopped at the residual stream.  Blocks of `hblocks` (a subset: hooks on their per-head inputs) run only their HEAD on the
-        module's code (_head_glue); the plan is entered behind their q, k, v.  Fills `cache`, returns the output."""
-        NP = self._NPOS
-        resid, b = start, 0
-        entry, acts = 0, ()                                      # the next plan run enters block b at this stage with these activations
-        for L in list(tblocks) + [None]:
-            stop = n_blocks if L is None else L
-            head_here = L is None and run_head
-            if stop > b or head_here or resid is None:
-                # the hooks of this run of plan blocks: strictly inside it as they are; at its end only what belongs to its last block
-                # (the next block's hook_resid_pre fires inside that block's module); at its start hook_resid_pre of block b by hand
-                sub = {}
-                for q, kinds in bh.items():
-                    if NP * b + entry < q < NP * stop:           # (entry > 0: what lies before fired inside _head_glue)
-                        sub[q] = kinds
-                    elif q == NP * stop and stop > b:
-                        k_ = kinds if L is None else {k: v for k, v in kinds.items() if k in ("mlp", "post")}
-                        if k_:
-                            sub[q] = k_
-                if resid is not None and b > 0 and stop > b and not entry:
-                    pre = bh.get(NP * b, {}).get("pre")
-                    if pre is not None:
-                        resid = pre(resid)
-                    if f"blocks.{b}.hook_resid_pre" in wanted:
-                        cache[f"blocks.{b}.hook_resid_pre"] = resid
-
-                def mine(n: str) -> bool:
-                    if n.startswith("blocks."):
-                        return b <= int(n.split(".", 2)[1]) < stop
-                    return (n in self._FINAL_NAMES and head_here) or (n not in self._FINAL_NAMES and b == 0 and resid is None)
-
-                seg_names = [n for n in names if mine(n) and not (resid is not None and n == f"blocks.{b}.hook_resid_pre")
-                             and not (entry and n.startswith(f"blocks.{b}.") and self._stage_of(n) < NP * b + entry)]
-                resid, c = self._run_native_segments(x, resid, seg_names, stop, head_here, sub, None, False,
-                                                     first_block=b, entry_stage=entry, entry_acts=acts)
-                cache.update(c)
-                entry, acts = 0, ()
-            if L is None:
-                break
-            if L in hblocks:
-                # the block's head on its own code (hooks on the per-head inputs / per-head ln1 fire there), the rest on the plan
-                resid, acts, rec = self._head_glue(L, resid, wanted)
-                cache.update(rec)
-                b, entry = L, 2                                  # PV_STAGE_QKV: q, k, v given, resid = the stream they add to
-                continue
-            resid, rec = self._torch_block_stage(L, resid, wanted)
-            cache.update(rec)
-            b = L + 1
-        return resid
-
-    def _head_glue(self, l: int, resid: torch.Tensor, wanted):
-        """Block l up to its q, k, v on the module's own code (transformer_block.py:80-109, attention.py:186-244): hook_resid_pre, the
-        per-head inputs with their flag-gated HookPoints, ln1 per input, the per-head projections with hook_q / hook_k / hook_v.
-        -> (resid_pre, (q, k, v), {name: cached tensor}); the plan resumes at PV_STAGE_QKV."""
-        cfg, blk = self.cfg, self.blocks[l]
-        rec: Dict[str, torch.Tensor] = {}
-        pre = f"blocks.{l}."
-        which = [pre + r for r in ("hook_resid_pre", "hook_attn_in", "hook_q_input", "hook_k_input", "hook_v_input", "ln1.hook_scale",
-                                   "ln1.hook_normalized", "attn.hook_q", "attn.hook_k", "attn.hook_v")]
-        handles = self._recording_hooks(which, wanted, rec)
-        try:
-            resid_pre = blk.hook_resid_pre(resid)
-            attn_in = resid_pre
-            if cfg.use_attn_in or cfg.use_split_qkv_input:
-                attn_in = resid_pre.unsqueeze(2).expand(-1, -1, cfg.n_heads, -1)
-            if cfg.use_attn_in:
-                attn_in = blk.hook_attn_in(attn_in.clone())
-            if cfg.use_split_qkv_input:
-                q_in, k_in, v_in = blk.hook_q_input(attn_in.clone()), blk.hook_k_input(attn_in.clone()), blk.hook_v_input(attn_in.clone())
-            else:
-                q_in = k_in = v_in = attn_in
-            q, k, v = blk.attn.calculate_qkv_matrices(blk.ln1(q_in), blk.ln1(k_in), blk.ln1(v_in))
-        finally:
-            for h in handles:
-                h.remove()
-        return resid_pre.contiguous(), (q.contiguous(), k.contiguous(), v.contiguous()), rec
-
-    def _stage_of(self, name: str) -> int:
-        """The stage (position scale: _NPOS per block) that produces a HookPoint's tensor; -1: embedding stage, _NPOS * n_layers: final."""
-        NP = self._NPOS
-        if name.startswith("blocks."):
-            _, l, rest = name.split(".", 2)
-            if rest == "hook_resid_pre" or rest.startswith("ln1.") or rest in ("hook_attn_in", "hook_q_input", "hook_k_input", "hook_v_input"):
-                st = 0
-            elif rest in ("attn.hook_q", "attn.hook_k", "attn.hook_v"):
-                st = 1
-            elif rest == "attn.hook_attn_scores":
-                st = 2
-            elif rest == "attn.hook_pattern":
-                st = 3
-            elif rest == "attn.hook_z":
-                st = 4
-            elif rest in ("hook_attn_out", "hook_resid_mid", "attn.hook_result"):
-                st = 5
-            elif rest.startswith("ln2.") or rest == "hook_mlp_in":
-                st = 6
-            elif rest == "mlp.hook_pre":
-                st = 7
-            elif rest.startswith("mlp."):
-                st = 8
-            else:
-                st = 9
-            return NP * int(l) + st
-        return -1 if name in ("hook_embed", "hook_pos_embed", "hook_full_embed", "hook_ln_pre") or name.startswith("ln_pre.") \
-            else NP * self.cfg.n_layers
-
-    def _torch_block_stage(self, l: int, resid: torch.Tensor, wanted):
-        """Block l on its own module (transformer_block.py:80-138): (its output, {name: cached tensor} of its HookPoints)."""
-        rec: Dict[str, torch.Tensor] = {}
-        pre = f"blocks.{l}."
-        handles = self._recording_hooks([n for n in self.hook_dict if n.startswith(pre)], wanted, rec)
-        try:
-            out = self.blocks[l](resid)
-        finally:
-            for h in handles:
-                h.remove()
-        return out.contiguous(), rec
-
-    def _recording_hooks(self, which, wanted, rec):
-        """forward hooks that note what the HookPoints of `which` pass on (registered behind the caller's hooks, like the caching
-        hooks of the PyTorch path: the cache holds the post-hook value); returns the handles"""
-        handles = []
-        for n in which:
-            hp = self.hook_dict.get(n)
-            if hp is not None and n in wanted:
-                handles.append(hp.register_forward_hook(lambda m, i, o, n=n: rec.__setitem__(n, o)))
-        return handles
-
-    def _torch_embedding_stage(self, x: torch.Tensor, wanted, n_blocks: int):
-        """base_vit.py:169-185 on the model's own modules: (the residual stream entering block 0, {name: cached tensor})."""
-        cfg = self.cfg
-        rec: Dict[str, torch.Tensor] = {}
-        first = "blocks.0.hook_resid_pre"
-        handles = self._recording_hooks(self._EMBED_NAMES + ((first,) if n_blocks > 0 else ()), wanted, rec)
-        try:
-            inp = x.to(cfg.dtype) if x.dtype != cfg.dtype else x
-            embed = self.hook_embed(self.embed(inp))
-            if cfg.use_cls_token:
-                embed = torch.cat((self.cls_token.expand(inp.shape[0], -1, -1), embed), dim=1)
-            residual = embed + self.hook_pos_embed(self.pos_embed(inp))
-            self.hook_full_embed(residual)                       # observe-only
-            if cfg.layer_norm_pre:
-                residual = self.hook_ln_pre(self.ln_pre(residual))
-            if n_blocks > 0:
-                residual = self.blocks[0].hook_resid_pre(residual)
-        finally:
-            for h in handles:
-                h.remove()
-        return residual.contiguous(), rec
-
-    def _torch_final_stage(self, residual: torch.Tensor, wanted):
-        """base_vit.py:192-217 on the model's own modules: (model output, {name: cached tensor})."""
-        cfg = self.cfg
-        rec: Dict[str, torch.Tensor] = {}
-        handles = self._recording_hooks(self._FINAL_NAMES, wanted, rec)
-        try:
-            x = self.ln_final(residual)
-            self.hook_ln_final(x)                                # observe-only
-            if cfg.classification_type == "gaap":
-                x = x.mean(dim=1)
-            elif cfg.classification_type == "cls":
-                x = x[:, 0]
-            if cfg.return_type != "pre_logits":
-                x = self.head(x)
-            self.hook_post_head_pre_normalize(x)                 # observe-only
-            if cfg.normalize_output:
-                x = F.normalize(x, dim=-1)
-        finally:
-            for h in handles:
-                h.remove()
-        return x, rec
-
-    def _run_native_segments(self, x: torch.Tensor, start_resid: Optional[torch.Tensor], names, n_blocks: int, run_head: bool, bh,
-                             device, remove_batch_dim: bool, first_block: int = 0, entry_stage: int = 0, entry_acts=()):
-        """The blocks (+ the head) on the HIP plan, split at the hooked positions of `bh`; start_resid: resume at block
-        `first_block` from this residual stream instead of starting from the pixels (what lies before ran elsewhere); entry_stage /
-        entry_acts: ... at that position INSIDE block first_block with the stage's activations (2 = q, k, v given: _head_glue)."""
-        cfg = self.cfg
-        nv = self._get_native(x.device)
-        NP = self._NPOS
-        end_pos = NP * n_blocks
-        # a hook at the very end fires only if its point is produced: "pre" of block n_blocks is not
-        bounds = sorted(q for q in bh if q < end_pos or (q == end_pos and ("post" in bh[q] or "mlp" in bh[q])))
-        if not bounds and not entry_stage:
-            tap_dst = getattr(self, "_tap_dst", None)             # (the activation store's own buffer slice, sae/store.py)
-            if start_resid is not None:
-                return nv.forward(self, None, names, n_blocks, run_head, cache_device=device, remove_batch_dim=remove_batch_dim,
-                                  first_block=first_block, resid_in=start_resid)
-            return nv.forward(self, x, names, n_blocks, run_head, cache_device=device, remove_batch_dim=remove_batch_dim,
-                              **({"tap_dst": tap_dst} if tap_dst else {}))
-        # ---- split plan: [0, q1) -> hooks -> [q1, q2) -> ... -> [qk, end) (+ head); positions count NP per block.
-        # Stage t = the computation between positions t and t + 1 (of block t // NP): 0 ln1 | 1 q, k, v | 2 scores | 3 softmax |
-        # 4 pattern v | 5 O-projection + residual | 6 ln2 | 7 MLP up to the pre-activation | 8 activation | 9 MLP output + residual.
-        wanted = set(names)
-        cache: Dict[str, torch.Tensor] = {}
-        ST_QKV, ST_O, ST_MLP = 1, 5, 9                          # stages of q / k / v, the O-projection, the MLP output
-
-        pos_of = self._stage_of                                 # the stage that produces a name (-1: embedding stage, NP * n_layers: final stage)
-
-        def renormalize(ln_mod: nn.Module, x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
-            """hook_normalized's tensor from an edited hook_scale, as the module computes it (layer_norm.py:88-93, :38-45)"""
-            xc = x.to(torch.float32) if cfg.dtype not in (torch.float32, torch.float64) else x
-            xc = xc - xc.mean(-1, keepdim=True)
-            out = xc / scale
-            return out * ln_mod.w + ln_mod.b if isinstance(ln_mod, LayerNorm) else out
-
-        p0, resid, acts, out = NP * first_block + entry_stage, start_resid, tuple(entry_acts), None
-        from_pixels = start_resid is None
-        assert (first_block == 0 and not entry_stage) or not from_pixels
-        for q in bounds + [None]:
-            last = q is None
-            p1 = end_pos if last else q
-            b1, s1 = divmod(p1, NP)                             # the segment ends at position s1 of block b1
-            blk = b1 if s1 else b1 - 1                          # the block its last stage lies in
-            seg = [n for n in names if (p0 == 0 or pos_of(n) >= p0) and pos_of(n) < (NP * cfg.n_layers + 1 if last else p1)
-                   and not ((p0 > 0 or not from_pixels) and p0 % NP == 0 and n == f"blocks.{p0 // NP}.hook_resid_pre")      # (the resumed tensor: set by hand)
-                   and self._FLAG_RE.fullmatch(n) is None]          # (a served flag-gated point is no tap: produced below)
-            hooks = {} if last else bh[q]
-            c: Dict[str, torch.Tensor] = {}
-            seg_in = resid
-            pre_inside = p0 < NP * b1 or (p0 == 0 and from_pixels)     # block b1's entry lies inside this segment
-            if p0 == p1 and not (last and run_head):
-                out = resid                                   # nothing left to run: the hooked residual is the output
-            else:
-                forced = []
-                if not last:
-                    pre_name, mid_name = f"blocks.{b1}.hook_resid_pre", f"blocks.{b1}.hook_resid_mid"
-                    v_name = f"blocks.{b1}.attn.hook_v"
-                    pre_f = [pre_name] if pre_inside else []
-                    mid_f = [mid_name] if p0 <= NP * b1 + ST_O else []           # resid_mid is produced inside this segment
-                    if s1 == 0:
-                        forced = [f"blocks.{blk}.hook_resid_post"]
-                        if "mlp" in hooks:
-                            forced += [f"blocks.{blk}.hook_mlp_out"] + ([f"blocks.{blk}.hook_resid_mid"] if p0 <= NP * blk + ST_O else [])
-                    elif s1 == 1:
-                        forced = [f"blocks.{b1}.ln1.hook_scale", f"blocks.{b1}.ln1.hook_normalized"] + pre_f
-                    elif s1 == 2:
-                        forced = [f"blocks.{b1}.attn.hook_{t}" for t in "qkv"] + pre_f
-                    elif s1 in (3, 4):
-                        # the resumed attention core reads v next to the edited scores / pattern: tapped when this segment
-                        # computes it, carried from the previous segment's activations otherwise
-                        forced = [f"blocks.{b1}.attn." + ("hook_attn_scores" if s1 == 3 else "hook_pattern")]
-                        forced += ([v_name] if p0 <= NP * b1 + ST_QKV else []) + pre_f
-                    elif s1 == 5:
-                        forced = [f"blocks.{b1}.attn.hook_z"] + pre_f
-                    elif s1 == 6:
-                        forced = [mid_name]
-                        if "attn" in hooks or "result" in hooks:
-                            forced += [f"blocks.{b1}.hook_attn_out"] + pre_f
-                        if "result" in hooks and p0 <= NP * b1 + 4:      # z is produced inside this segment (else: carried from a hook on z)
-                            forced += [f"blocks.{b1}.attn.hook_z"]
-                    elif s1 == 7:
-                        forced = [f"blocks.{b1}.ln2.hook_scale", f"blocks.{b1}.ln2.hook_normalized"] + mid_f
-                    elif s1 == 8:
-                        forced = [f"blocks.{b1}.mlp.hook_pre"] + mid_f
-                    else:
-                        forced = [f"blocks.{b1}.mlp.hook_post"] + mid_f
-                req = seg + [n for n in forced if n not in seg]
-                start_px = p0 == 0 and from_pixels
-                out, c = nv.forward(self, x if start_px else None, req, b1, last and run_head, first_block=p0 // NP,
-                                    resid_in=None if start_px else resid, entry_stage=p0 % NP, exit_stage=s1, act_in=acts)
-                cache.update({k: v for k, v in c.items() if k in wanted})
-            if last:
-                break
-            prev_acts, acts = acts, ()
-            if s1 in (1, 7):
-                # a LayerNorm of block b1: hook_scale, then hook_normalized recomputed from the (edited) scale as the module does,
-                # then hook_normalized's own hooks; the block resumes from the fp32 tensor they leave (rounded to the storage
-                # dtype by the kernel, layer_norm.py:93)
-                which = "ln1" if s1 == 1 else "ln2"
-                carried = f"blocks.{b1}.hook_resid_pre" if s1 == 1 else f"blocks.{b1}.hook_resid_mid"
-                resid = c.get(carried, seg_in)
-                s_name, n_name = f"blocks.{b1}.{which}.hook_scale", f"blocks.{b1}.{which}.hook_normalized"
-                scale, norm = c[s_name], c[n_name]
-                if s1 == 7 and "mlpin" in hooks:
-                    # use_hook_mlp_in (transformer_block.py:125-129): the hook sees a COPY of resid_mid, the MLP half continues from
-                    # what it returns, the residual stream it adds to stays resid_mid; ln2 of the edited tensor as the module computes it
-                    m_name = f"blocks.{b1}.hook_mlp_in"
-                    mlp_in = hooks["mlpin"](resid.clone())
-                    if m_name in wanted:
-                        cache[m_name] = mlp_in
-                    ln_mod = self.blocks[b1].ln2
-                    xc = mlp_in.to(torch.float32) if cfg.dtype not in (torch.float32, torch.float64) else mlp_in
-                    xc = xc - xc.mean(-1, keepdim=True)
-                    scale = (xc.pow(2).mean(-1, keepdim=True) + ln_mod.eps).sqrt()
-                    norm = renormalize(ln_mod, mlp_in, scale)
-                if which + "s" in hooks:
-                    scale = hooks[which + "s"](scale)
-                    norm = renormalize(getattr(self.blocks[b1], which), resid, scale)
-                if which + "n" in hooks:
-                    norm = hooks[which + "n"](norm)
-                if s_name in wanted:
-                    cache[s_name] = scale
-                if n_name in wanted:
-                    cache[n_name] = norm
-                acts = (norm,)
-            elif s1 in (2, 3, 4, 5, 8, 9):
-                # inside the attention half / the MLP: the hooks see the stage's activations (attention.py:135-152, 186-281;
-                # mlp.py:65-80), the rest of the block resumes from what they return; the residual stream the block adds to
-                # is carried along untouched
-                kinds = {2: ("q", "k", "v"), 3: ("scores",), 4: ("pattern",), 5: ("z",), 8: ("mlppre",), 9: ("mlppost",)}[s1]
-                vals = []
-                for kind in kinds:
-                    nm = f"blocks.{b1}." + {"q": "attn.hook_q", "k": "attn.hook_k", "v": "attn.hook_v", "scores": "attn.hook_attn_scores",
-                                            "pattern": "attn.hook_pattern", "z": "attn.hook_z", "mlppre": "mlp.hook_pre",
-                                            "mlppost": "mlp.hook_post"}[kind]
-                    t = c[nm]
-                    if kind in hooks:
-                        t = hooks[kind](t)
-                    if nm in wanted:
-                        cache[nm] = t
-                    vals.append(t)
-                if s1 in (3, 4):
-                    # v for the resumed core: this segment's tap, or what the previous position handed on ((q, k, v) | (scores, v))
-                    vals.append(c[v_name] if v_name in c else prev_acts[-1])
-                acts = tuple(vals)
-                carried = f"blocks.{b1}.hook_resid_mid" if s1 >= 8 else f"blocks.{b1}.hook_resid_pre"
-                resid = c.get(carried, seg_in)
-            elif s1 == 6:
-                # after block b1's attention half: hook_attn_out rebuilds resid_mid = resid_pre + attn_out with the
-                # kernel's rounding (transformer_block.py:117-124), then hook_resid_mid
-                resid = c[f"blocks.{b1}.hook_resid_mid"]
-                if "attn" in hooks or "result" in hooks:
-                    a_name = f"blocks.{b1}.hook_attn_out"
-                    attn_out = c[a_name]
-                    if "result" in hooks:
-                        # use_attn_result (attention.py:155-183): z against W_O per head, the hook on the per-head results, their sum
-                        # + b_O is what the block adds -- one batched product and a reduction folded back into the stream
-                        z_name, r_name = f"blocks.{b1}.attn.hook_z", f"blocks.{b1}.attn.hook_result"
-                        attn = self.blocks[b1].attn
-                        result = hooks["result"](torch.einsum("bqhe,hed->bqhd", c[z_name] if z_name in c else prev_acts[0], attn.W_O))
-                        if r_name in wanted:
-                            cache[r_name] = result
-                        attn_out = result.sum(dim=2) + attn.b_O
-                    if "attn" in hooks:
-                        attn_out = hooks["attn"](attn_out)
-                    if a_name in wanted:
-                        cache[a_name] = attn_out
-                    pre = c.get(f"blocks.{b1}.hook_resid_pre", seg_in)
-                    resid = pre + attn_out.to(pre.dtype)
-                if "mid" in hooks:
-                    resid = hooks["mid"](resid)
-                if f"blocks.{b1}.hook_resid_mid" in wanted:
-                    cache[f"blocks.{b1}.hook_resid_mid"] = resid
-            else:
-                # entering block blk+1: hook_mlp_out rebuilds resid_post = resid_mid + mlp_out (block :131-134), then
-                # hook_resid_post, then the next block's hook_resid_pre
-                post_name = f"blocks.{blk}.hook_resid_post"
-                resid = c[post_name]
-                if "mlp" in hooks:
-                    m_name = f"blocks.{blk}.hook_mlp_out"
-                    mlp_out = hooks["mlp"](c[m_name])
-                    if m_name in wanted:
-                        cache[m_name] = mlp_out
-                    mid = c.get(f"blocks.{blk}.hook_resid_mid", seg_in)
-                    resid = mid + mlp_out.to(mid.dtype)
-                if "post" in hooks:
-                    resid = hooks["post"](resid)
-                if post_name in wanted:
-                    cache[post_name] = resid
-                if p1 < end_pos:
-                    pre_name = f"blocks.{blk + 1}.hook_resid_pre"
-                    if "pre" in hooks:
-                        resid = hooks["pre"](resid)
-                    if pre_name in wanted:
-                        cache[pre_name] = resid
-            p0 = p1
-        if out is None:
-            out = resid
-        ordered: Dict[str, torch.Tensor] = {}
-        for n in names:
-            t = cache[n]
-            if device is not None:
-                t = t.to(device)
-            ordered[n] = t[0] if remove_batch_dim else t
-        return out, ordered
 
     # ------------------------------------------------------------------------------ construction helpers of the reference
     @classmethod
