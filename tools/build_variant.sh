@@ -2,6 +2,8 @@
 # tools/build_variant.sh NAME [-DFLAG ...]: one source of csrc/ (SRC=gemm by default) rebuilt with extra defines into
 # tools/variants/libpvnative_NAME.so (the other objects come from the regular in-tree build); select it with
 # PV_NATIVE_LIB=tools/variants/libpvnative_NAME.so
+# Switches of the ViT forward's kernels: -DPV_STORE_CONSUMED=P -DPV_STORE_TAP=P (store policy of the large outputs, P = 0 plain,
+# 1 nt, 2 sc1, 3 sc1 nt; pv_common.hpp: SRC="gemm rowops attention"), -DPV_ATTN_V_ROWS=0, -DPV_ATTN_VROWS_WAVES=3 (SRC=attention)
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift

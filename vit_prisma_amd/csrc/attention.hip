@@ -291,23 +291,42 @@ int launch_attn(const AttnParams& p, hipStream_t stream) {
 // ---------------------------------------------------------------------------------------------------
 // Whole-head-per-WAVE variant (bf16, T <= 64, T even): the B/32 shape (T = 50, 6144 heads at bs = 512).
 //   The workgroup kernel above spends its time in barriers between four waves that share one 50 x 50
-//   problem (112 us per layer at bs = 512 against ~45 us of HBM time).  Here a wave owns one (image, head):
-//   no workgroup barrier anywhere, 9 KB of LDS per wave (16 waves per CU), every phase ordered by the wave's
-//   own in-order LDS queue:
-//     1  K, Q fragments straight from global (buffer loads clipped to the head's T rows: pad rows read 0)
+//   problem (112 us per layer at bs = 512 against ~35 us of HBM time).  Here a wave owns one (image, head):
+//   no workgroup barrier anywhere, 9 KB of LDS per wave (16 waves per CU = 4 per SIMD), every phase ordered by the
+//   wave's own in-order LDS queue:
+//     0  V as WHOLE rows (eight 16-byte loads per lane) through the LDS rows, read back transposed (ds_read_b64_tr_b16)
+//        into the 32 registers of the P V operand, which are held to phase 6
+//     1  K, Q rows the same way (buffer loads clipped to the head's T rows: pad rows read 0), read back as fragments
 //     2  S = Q K^T on MFMA, scaled + rounded to bf16 -> LDS [64][72] (144-byte rows)
 //     3  hook_attn_scores: the head's T*T bf16 block leaves as flat 16-byte chunks (it is contiguous in HBM)
 //     4  softmax with lane r owning row r (8 ds_read_b128, all math in registers), P written back in place
 //     5  hook_pattern: flat copy as in 3
-//     6  z = P V on MFMA: P fragments from LDS, V fragments as 2-byte buffer loads (a lane needs 8 keys of
-//        ONE d_head column: k-strided in HBM, but 32 lanes cover 64 contiguous bytes of each key row)
+//     6  z = P V on MFMA: P fragments from LDS, V fragments from phase 0
+//        (-DPV_ATTN_V_ROWS=0, and the direct form: V fragments as 2-byte buffer loads here -- a lane needs 8 keys of ONE
+//        d_head column, k-strided in HBM: 64 loads per lane whose latency nothing hides, every 128-byte V row looked up
+//        many times by the texture addresser)
 //     7  z staged through the same LDS rows -> 16-byte row stores
+//   What the compiler makes of it is part of the design (tests/test_kernel_resources_cpu.py holds it to that): without
+//   the second launch bound hipcc parked the z accumulators in 64 AGPRs on top of 105 VGPRs = 169 registers = TWO waves
+//   per SIMD, half of what the LDS was sized for.  With it: <64, true, true> 128 VGPRs, <32, true, true> 112, the forms
+//   without V rows 98 - 105; no AGPRs, no scratch, 4 waves per SIMD.  The V-rows form only fits because the Q rows are
+//   requested after the V operand has been read (V, K and Q rows all in flight beside it: 138 registers, 3 waves).
+//   Measured per launch at bs = 512 (MEASURED.md): 2 waves 48.7 - 50.1 us, 4 waves 41.4 - 42.8, 4 waves + V rows 39.8 - 41.2.
 // ---------------------------------------------------------------------------------------------------
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 constexpr int AW_ROW = 144;                 // bytes per LDS row: 64 bf16 + 16 pad (conflict-free b128 rows)
 
-template <int DH, bool STAGE = true>
-__global__ __launch_bounds__(256) void attn_wave_kernel(const AttnParams p) {
+typedef short i16x4_t __attribute__((ext_vector_type(4)));
+#ifndef PV_ATTN_V_ROWS
+#define PV_ATTN_V_ROWS 1                    // 0 (A/B builds): V fragments as 2-byte buffer loads after the softmax
+#endif
+#ifndef PV_ATTN_VROWS_WAVES
+#define PV_ATTN_VROWS_WAVES 4               // waves per SIMD the V-rows form is compiled for (A/B builds: 3)
+#endif
+
+template <int DH, bool STAGE = true, bool VROWS = STAGE && PV_ATTN_V_ROWS>
+__global__ __launch_bounds__(256, VROWS ? PV_ATTN_VROWS_WAVES : 4) void attn_wave_kernel(const AttnParams p) {
+    static_assert(STAGE || !VROWS, "whole V rows go through the staging rows");
     __shared__ __attribute__((aligned(16))) unsigned char smem[4][64 * AW_ROW];
     constexpr int NKS = DH / 16;            // k16 steps of Q K^T
     constexpr int NTN = DH / 32;            // 32-wide d_head tiles of P V
@@ -338,12 +357,48 @@ __global__ __launch_bounds__(256) void attn_wave_kernel(const AttnParams p) {
     const int s_row = lane / CPR, s_ch = lane % CPR;
     u32x4_t kf[2][NKS];
     u32x4_t qrow[STAGE ? NLD : 1];
+    u32x4_t vf[VROWS ? 4 : 1][NTN];                                   // VROWS: the V^T operand of all four k16 steps of phase 6
     if constexpr (STAGE) {
         u32x4_t krow[NLD];
+        u32x4_t vrow[VROWS ? NLD : 1];
+        if constexpr (VROWS) {
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) vrow[i] = __builtin_amdgcn_raw_buffer_load_b128(rsV, (unsigned)(i * RPI + s_row) * tokb + s_ch * 16, 0, 0);
+        }
 #pragma unroll
         for (int i = 0; i < NLD; ++i) krow[i] = __builtin_amdgcn_raw_buffer_load_b128(rsK, (unsigned)(i * RPI + s_row) * tokb + s_ch * 16, 0, 0);
+        if constexpr (!VROWS) {
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) qrow[i] = __builtin_amdgcn_raw_buffer_load_b128(rsQ, (unsigned)(i * RPI + s_row) * tokb + s_ch * 16, 0, 0);
+            for (int i = 0; i < NLD; ++i) qrow[i] = __builtin_amdgcn_raw_buffer_load_b128(rsQ, (unsigned)(i * RPI + s_row) * tokb + s_ch * 16, 0, 0);
+        }
+        if constexpr (VROWS) {
+            // V first, while the K rows are still in flight: whole rows into the LDS rows, read back TRANSPOSED (a lane of phase 6
+            // needs 8 consecutive keys of ONE d_head column).  ds_read_b64_tr_b16 works per 16-lane group on a block of 4 rows x
+            // 16 columns: lane 4 q + c of the group gives the address of row q, columns 4 c .. 4 c + 3, and receives column
+            // (lane & 15) of the four rows.  Group g of the wave = half g >> 1, columns (g & 1) * 16 ..: lane (l31, half) gets
+            // keys r0 .. r0 + 3 of column tn * 32 + l31 -- the words the 2-byte loads of the other form assemble.  The whole wave
+            // is active here (the gather needs that); pad rows (>= T) were clipped to zero by the buffer loads.
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) *reinterpret_cast<u32x4_t*>(SP + (i * RPI + s_row) * AW_ROW + s_ch * 16) = vrow[i];
+            __builtin_amdgcn_wave_barrier();
+            const int grp = lane >> 4, gq = (lane >> 2) & 3, gc = lane & 3;
+            typedef __attribute__((address_space(3))) i16x4_t lds_i16x4_t;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int tn = 0; tn < NTN; ++tn) {
+                    unsigned char* a = SP + (ks * 16 + (grp >> 1) * 8 + gq) * AW_ROW + (tn * 32 + (grp & 1) * 16 + 4 * gc) * 2;
+                    const i16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4_t*)a);
+                    const i16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4_t*)(a + 4 * AW_ROW));
+                    const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+                    vf[ks][tn] = u32x4_t{l2.x, l2.y, h2.x, h2.y};
+                }
+            __builtin_amdgcn_wave_barrier();
+            // (Q only now: with V, K and Q rows all in flight beside the 32 registers of vf the kernel needs 138 registers, three
+            // waves per SIMD; the Q rows arrive under the K staging below)
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) qrow[i] = __builtin_amdgcn_raw_buffer_load_b128(rsQ, (unsigned)(i * RPI + s_row) * tokb + s_ch * 16, 0, 0);
+        }
 #pragma unroll
         for (int i = 0; i < NLD; ++i) *reinterpret_cast<u32x4_t*>(SP + (i * RPI + s_row) * AW_ROW + s_ch * 16) = krow[i];
         __builtin_amdgcn_wave_barrier();
@@ -492,9 +547,13 @@ __global__ __launch_bounds__(256) void attn_wave_kernel(const AttnParams p) {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
         if (ks * 16 >= T_) break;                                        // keys beyond T: P and V are zero there
-        u32x4_t vf[NTN];
+        u32x4_t vk[NTN];
 #pragma unroll
         for (int tn = 0; tn < NTN; ++tn) {
+            if constexpr (VROWS) {
+                vk[tn] = vf[ks][tn];
+                continue;
+            }
             uint32_t w[4];
 #pragma unroll
             for (int q2 = 0; q2 < 4; ++q2) {
@@ -504,14 +563,14 @@ __global__ __launch_bounds__(256) void attn_wave_kernel(const AttnParams p) {
                 const uint32_t hi = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsV, o + tokb, 0, 0);
                 w[q2] = lo | (hi << 16);
             }
-            vf[tn] = u32x4_t{w[0], w[1], w[2], w[3]};
+            vk[tn] = u32x4_t{w[0], w[1], w[2], w[3]};
         }
 #pragma unroll
         for (int tq = 0; tq < 2; ++tq) {
             const uint4 pa = *reinterpret_cast<const uint4*>(SP + (tq * 32 + l31) * AW_ROW + ks * 32 + half * 16);
 #pragma unroll
             for (int tn = 0; tn < NTN; ++tn)
-                zacc[tq][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[tn]),      // z^T = V^T P^T
+                zacc[tq][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vk[tn]),      // z^T = V^T P^T
                                                                        __builtin_bit_cast(bf16x8, pa), zacc[tq][tn], 0, 0, 0);
         }
     }
@@ -533,8 +592,8 @@ __global__ __launch_bounds__(256) void attn_wave_kernel(const AttnParams p) {
         bf16_t* zb = reinterpret_cast<bf16_t*>(p.z) + head_off;
         for (int c = lane; c < T_ * CPR; c += 64) {
             const int row = c / CPR, ch = c - row * CPR;
-            *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(zb) + (int64_t)row * tokb + ch * 16) =
-                *reinterpret_cast<const uint4*>(SP + row * AW_ROW + ch * 16);
+            const uint4 zr = *reinterpret_cast<const uint4*>(SP + row * AW_ROW + ch * 16);
+            pv_store16_consumed<pv_u32x4_a16>(reinterpret_cast<unsigned char*>(zb) + (int64_t)row * tokb + ch * 16, zr.x, zr.y, zr.z, zr.w);
         }
     }
 }

@@ -163,6 +163,8 @@ __device__ __forceinline__ float act_any(float x, int act) {
     }
 }
 
+// (store policy, pv_common.hpp: the run-time epilogues put every 16-byte store in the CONSUMED class, their tap outputs included --
+// they have always been plain stores here, and these kernels are not on the bf16 forwards' hot path; the ragged tail stays scalar)
 template <typename T>
 __device__ __forceinline__ void epilogue8(const GemmParams& p, float (&v)[8], int gm, int gn) {
     T* out0 = reinterpret_cast<T*>(p.out0);
@@ -184,25 +186,25 @@ __device__ __forceinline__ void epilogue8(const GemmParams& p, float (&v)[8], in
             for (int i = 0; i < 8; ++i) v[i] += b[i];
         }
         if (p.epi == PV_EPI_BIAS || p.epi == PV_EPI_QKV) {
-            store8(out0 + (int64_t)gm * p.ldo + col, v);
+            store8_consumed(out0 + (int64_t)gm * p.ldo + col, v);
         } else if (p.epi == PV_EPI_RESID) {
             // attn_out / mlp_out is rounded to the storage dtype first (it is what the reference
             // adds to the residual: transformer_block.py:122-124, :134)
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = DT<T>::round(v[i]);
-            if (out0) store8(out0 + (int64_t)gm * p.ldo + gn, v);
+            if (out0) store8_consumed(out0 + (int64_t)gm * p.ldo + gn, v);
             float r[8];
             load8(reinterpret_cast<const T*>(p.resid) + (int64_t)gm * p.ldr + gn, r);
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] += r[i];
-            store8(out1 + (int64_t)gm * p.ldo + gn, v);
+            store8_consumed(out1 + (int64_t)gm * p.ldo + gn, v);
         } else {  // PV_EPI_ACT: mlp.py:67-72, activation applied to the stored pre-activation
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = DT<T>::round(v[i]);
-            if (out0) store8(out0 + (int64_t)gm * p.ldo + gn, v);
+            if (out0) store8_consumed(out0 + (int64_t)gm * p.ldo + gn, v);
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = act_any<T>(v[i], p.act);
-            store8(out1 + (int64_t)gm * p.ldo + gn, v);
+            store8_consumed(out1 + (int64_t)gm * p.ldo + gn, v);
         }
     } else {
         for (int i = 0; i < nvalid; ++i) {
@@ -248,25 +250,25 @@ __device__ __forceinline__ void epilogue8_pre(const GemmParams& p, float (&v)[8]
         v[2 * i + 1] += __uint_as_float(bw[i] & 0xffff0000u);
     }
     if (p.epi == PV_EPI_BIAS || p.epi == PV_EPI_QKV) {
-        store8(out0 + (int64_t)gm * p.ldo + col, v);
+        store8_consumed(out0 + (int64_t)gm * p.ldo + col, v);
     } else if (p.epi == PV_EPI_RESID) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = DT<T>::round(v[i]);
-        if (out0) store8(out0 + (int64_t)gm * p.ldo + gn, v);
+        if (out0) store8_consumed(out0 + (int64_t)gm * p.ldo + gn, v);
         const uint32_t rw[4] = {res.x, res.y, res.z, res.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             v[2 * i] += __uint_as_float(rw[i] << 16);
             v[2 * i + 1] += __uint_as_float(rw[i] & 0xffff0000u);
         }
-        store8(out1 + (int64_t)gm * p.ldo + gn, v);
+        store8_consumed(out1 + (int64_t)gm * p.ldo + gn, v);
     } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = DT<T>::round(v[i]);
-        if (out0) store8(out0 + (int64_t)gm * p.ldo + gn, v);
+        if (out0) store8_consumed(out0 + (int64_t)gm * p.ldo + gn, v);
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = act_any<T>(v[i], p.act);
-        store8(out1 + (int64_t)gm * p.ldo + gn, v);
+        store8_consumed(out1 + (int64_t)gm * p.ldo + gn, v);
     }
 }
 
@@ -733,7 +735,7 @@ __device__ __forceinline__ void epi8_bf16(const float4& x0, const float4& x1, co
     uint4 r;
     r.x = pack2(v[0]); r.y = pack2(v[1]); r.z = pack2(v[2]); r.w = pack2(v[3]);
     if constexpr (EPI == PV_EPI_BIAS || EPI == PV_EPI_QKV) {
-        *reinterpret_cast<uint4*>(o0) = r;
+        pv_store16_consumed<pv_u32x4_a16>(o0, r.x, r.y, r.z, r.w);
     } else {
         // the stored (bf16-rounded) value is what the reference carries on: transformer_block.py:122-124, :134;
         // mlp.py:67-72
@@ -749,7 +751,7 @@ __device__ __forceinline__ void epi8_bf16(const float4& x0, const float4& x1, co
             for (int i = 0; i < 4; ++i) v[i] = act2<ACT>(unpack2(rw[i]));
         }
         y.x = pack2(v[0]); y.y = pack2(v[1]); y.z = pack2(v[2]); y.w = pack2(v[3]);
-        *reinterpret_cast<uint4*>(o1) = y;
+        pv_store16_consumed<pv_u32x4_a16>(o1, y.x, y.y, y.z, y.w);
     }
 }
 

@@ -101,22 +101,77 @@ __device__ __forceinline__ void store8(bf16_t* p, const float (&v)[8]) {
     *reinterpret_cast<uint4*>(p) = a;
 }
 
-// 16 bytes to a TAP-ONLY destination (a cache entry nothing on the device reads back: the pre-activation / attn_out / mlp_out taps
-// of the GEMM epilogues, LayerNorm's fp32 hook_normalized, the attention scores / pattern): a nontemporal store, so that the tap
-// stream does not push the next kernel's operands (the tensor written beside it) out of the L2 / MALL.  Measured on the B/32
-// forward: MLP-2 131 -> 115 us with its A operand (mlp.hook_post) no longer evicted by the mlp.hook_pre tap (profiles/r04_notes.md).
-// V: one of the vector types below (the destination's alignment).  -DPV_NO_NT (A/B builds): plain stores.
+// ---------------------------------------------------------------------------------------------
+// Store policy of the forward's large outputs: every 16-byte store of one goes through pv_store16_as<POLICY, V>.
+//   PV_ST_PLAIN    global_store_dwordx4            the line stays (dirty) in the storing XCD's L2
+//   PV_ST_NT       ... nt                          streaming hint; still not write-through
+//   PV_ST_SC1      ... sc1                         write-through: the line leaves the L2 while the kernel runs, so the
+//                                                  write-back at the kernel's end has nothing left to do
+//   PV_ST_SC1_NT   ... sc1 nt
+// Two classes, each with a compile-time policy (A/B builds: tools/build_variant.sh NAME -DPV_STORE_CONSUMED=2 ...):
+//   CONSUMED  read back by a later kernel of the same forward: q / k / v, z, resid_mid / resid_post, the LayerNorm output,
+//             mlp.hook_post, hook_embed, ...                                               PV_STORE_CONSUMED, default plain
+//   TAP       a cache entry nothing on the device reads back: the pre-activation / attn_out / mlp_out taps of the GEMM
+//             epilogues, LayerNorm's fp32 hook_normalized, the attention scores / pattern.  Nontemporal, so that the tap stream
+//             does not push the next kernel's operands (the tensor written beside it) out of the L2 / MALL.  Measured on the
+//             B/32 forward: MLP-2 131 -> 115 us with its A operand (mlp.hook_post) no longer evicted by the mlp.hook_pre tap
+//             (profiles/r04_notes.md).                                PV_STORE_TAP, default nt (-DPV_NO_NT: plain)
+// Only 16-byte vector stores take a policy: a narrower sc1 store is one fabric write each (2.7 - 12 x the time per byte), so
+// the few narrow ones (hook_scale, ragged row ends) stay plain.
+// V: one of the vector types below (the destination's alignment; gfx950 global memory takes unaligned dwordx4 stores).
+// ---------------------------------------------------------------------------------------------
+#define PV_ST_PLAIN 0
+#define PV_ST_NT 1
+#define PV_ST_SC1 2
+#define PV_ST_SC1_NT 3
+#ifndef PV_STORE_CONSUMED
+#define PV_STORE_CONSUMED PV_ST_PLAIN
+#endif
+#ifndef PV_STORE_TAP
+#ifdef PV_NO_NT
+#define PV_STORE_TAP PV_ST_PLAIN
+#else
+#define PV_STORE_TAP PV_ST_NT
+#endif
+#endif
 typedef uint32_t pv_u32x4_a16 __attribute__((ext_vector_type(4)));
 typedef uint32_t pv_u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t pv_u32x4_a2 __attribute__((ext_vector_type(4), aligned(2)));
+template <int POLICY, typename V>
+__device__ __forceinline__ void pv_store16_as(void* p, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
+    static_assert(POLICY >= PV_ST_PLAIN && POLICY <= PV_ST_SC1_NT, "store policy");
+    if constexpr (POLICY == PV_ST_PLAIN) {
+        if constexpr (alignof(V) == 16) *reinterpret_cast<uint4*>(p) = make_uint4(x, y, z, w);
+        else *reinterpret_cast<V*>(p) = V{x, y, z, w};
+    } else if constexpr (POLICY == PV_ST_NT) {
+        __builtin_nontemporal_store(V{x, y, z, w}, reinterpret_cast<V*>(p));
+    } else {
+        // no builtin stores through a plain pointer with the sc1 bit.  The trailing s_nop keeps the compiler's next
+        // instruction from overwriting the four data registers before the store has read them.
+        const pv_u32x4_a16 v = {x, y, z, w};
+        if constexpr (POLICY == PV_ST_SC1) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+        else asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+    }
+}
+template <typename V>
+__device__ __forceinline__ void pv_store16_consumed(void* p, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
+    pv_store16_as<PV_STORE_CONSUMED, V>(p, x, y, z, w);
+}
 template <typename V>
 __device__ __forceinline__ void pv_store16_stream(void* p, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
-#ifdef PV_NO_NT
-    *reinterpret_cast<V*>(p) = V{x, y, z, w};
-#else
-    __builtin_nontemporal_store(V{x, y, z, w}, reinterpret_cast<V*>(p));
-#endif
+    pv_store16_as<PV_STORE_TAP, V>(p, x, y, z, w);
 }
+// 8 values to a CONSUMED destination (store8 above: the same bytes with plain stores, whatever the policy)
+__device__ __forceinline__ void store8_consumed(float* p, const float (&v)[8]) {
+    if constexpr (PV_STORE_CONSUMED == PV_ST_PLAIN) return store8(p, v);
+    pv_store16_consumed<pv_u32x4_a16>(p, __float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
+    pv_store16_consumed<pv_u32x4_a16>(p + 4, __float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
+}
+__device__ __forceinline__ void store8_consumed(bf16_t* p, const float (&v)[8]) {
+    if constexpr (PV_STORE_CONSUMED == PV_ST_PLAIN) return store8(p, v);
+    pv_store16_consumed<pv_u32x4_a16>(p, pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+}
+// 8 values to a TAP destination
 __device__ __forceinline__ void store8_stream(float* p, const float (&v)[8]) {
     pv_store16_stream<pv_u32x4_a16>(p, __float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
     pv_store16_stream<pv_u32x4_a16>(p + 4, __float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const LnParams p) {
                 load8(reinterpret_cast<const T*>(p.pos) + (int64_t)t * d + ch * 8, pos);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) x[c][i] = DT<T>::round(e[i] + pos[i]);
-                if (p.full_out) store8(reinterpret_cast<T*>(p.full_out) + (int64_t)row * d + ch * 8, x[c]);
+                if (p.full_out) store8_consumed(reinterpret_cast<T*>(p.full_out) + (int64_t)row * d + ch * 8, x[c]);
             } else {
                 load8(reinterpret_cast<const T*>(p.x) + (int64_t)row * p.ldx + ch * 8, x[c]);
             }
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const LnParams p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) y[i] = (x[c][i] / scale) * w[i] + b[i];
             if (p.norm_f32_out) store8_stream(p.norm_f32_out + (int64_t)row * d + ch * 8, y);   // (the fp32 tap of bf16 mode)
-            if (p.out) store8(reinterpret_cast<T*>(p.out) + (int64_t)row * d + ch * 8, y);
+            if (p.out) store8_consumed(reinterpret_cast<T*>(p.out) + (int64_t)row * d + ch * 8, y);
         }
     }
 }
