@@ -3,11 +3,11 @@
 The designs of these kernels are stated in waves per SIMD: LDS blocks are sized for them, latency hiding is reasoned
 from them.  Twice the shipped binary did not have the occupancy its header comment promised (the SAE select kernel six-deep
 instead of eight; ``attn_wave_kernel<64, true>`` with its accumulators parked in 64 AGPRs on top of 105 VGPRs: two waves per
-SIMD where its LDS was sized for four).  hipcc cross-compiles without a GPU, so this is checked here: attention.hip, rowops.hip
-and gemm.hip are compiled with build.py's flags plus ``-Rpass-analysis=kernel-resource-usage`` and the report is held against
+SIMD where its LDS was sized for four).  hipcc cross-compiles without a GPU, so this is checked here: attention.hip, rowops.hip,
+gemm.hip and sae_enc.hip are compiled with build.py's flags plus ``-Rpass-analysis=kernel-resource-usage`` and the report is held against
 the table below.
 
-Not ``gpu``-marked; skipped where no hipcc is found.  About a minute of compiling (the three sources in parallel).
+Not ``gpu``-marked; skipped where no hipcc is found.  About a minute of compiling (the four sources in parallel).
 """
 from __future__ import annotations
 
@@ -20,7 +20,7 @@ import pytest
 
 from vit_prisma_amd import build as pv_build
 
-SOURCES = ("attention.hip", "rowops.hip", "gemm.hip")
+SOURCES = ("attention.hip", "rowops.hip", "gemm.hip", "sae_enc.hip")
 
 # instance -> (source, its mangled name up to the argument list, least waves per SIMD the design states).  Scratch must be 0 for
 # all.  The floor is the DESIGN's figure, not a snapshot: a kernel may do better.  (Mangled: t = unsigned short = bf16 storage,
@@ -42,6 +42,15 @@ EXPECTED = {
     "gemm_kernel_v7<bf16, 5, 2, 0, 2>": ("gemm.hip", "14gemm_kernel_v7ItLi5ELi2ELi0ELi2EEEv", 2),
     "gemm_kernel_v7<bf16, 5, 0, 0, 0>": ("gemm.hip", "14gemm_kernel_v7ItLi5ELi0ELi0ELi0EEEv", 2),
     "gemm_kernel_v4<bf16>": ("gemm.hip", "14gemm_kernel_v4ItEEv", 3),
+    # every user of the shared K loop (kloop.hpp): the pipelined 64-byte-slab form and the persistent kernel at MB = 4, and the SAE
+    # filter GEMM <MODE, LP, ONE, MB> -- the bench shape's filter pass with and without the one-round epilogue, the 128-row sample
+    # pass, the pipelined sample pass
+    "gemm_kernel_v7<bf16, 4, 3, 1, 1>": ("gemm.hip", "14gemm_kernel_v7ItLi4ELi3ELi1ELi1EEEv", 2),
+    "gemm_kernel_v8<bf16, 4, 2, 0>": ("gemm.hip", "14gemm_kernel_v8ItLi4ELi2ELi0EEEv", 2),
+    "sae_enc_gemm_kernel<1, 2, false, 4>": ("sae_enc.hip", "19sae_enc_gemm_kernelILi1ELi2ELb0ELi4EEEv", 2),
+    "sae_enc_gemm_kernel<1, 2, true, 4>": ("sae_enc.hip", "19sae_enc_gemm_kernelILi1ELi2ELb1ELi4EEEv", 2),
+    "sae_enc_gemm_kernel<0, 2, false, 2>": ("sae_enc.hip", "19sae_enc_gemm_kernelILi0ELi2ELb0ELi2EEEv", 2),
+    "sae_enc_gemm_kernel<0, 1, false, 4>": ("sae_enc.hip", "19sae_enc_gemm_kernelILi0ELi1ELb0ELi4EEEv", 2),
 }
 
 _FIELDS = {

@@ -567,7 +567,9 @@ def test_gated_topk_and_unequal_width_transcoder_on_rccl_world1_equal_the_oracle
 # ---------------------------------------------------------------------------------------------------
 def _both_paths(eng, x, tuning, loop=-1):
     tuning("reset")
-    tuning("gemm_loop", loop)                      # K loop of the filter GEMM: -1 software-pipelined (default), 0 barrier-then-fetch
+    # K loop of the filter GEMM: -1 auto (full-line 128-byte slabs where d_in % 64 == 0, else pipelined 64-byte slabs where
+    # d_in % 32 == 0, else barrier-then-fetch), 0 barrier-then-fetch, 1 pipelined 64-byte slabs where legal, 2 as auto
+    tuning("gemm_loop", loop)
     idx_f, val_f, mu_f, sd_f = (t.clone() for t in eng.encode_topk(x))
     n_fb = eng.fallback_rows()
     tuning("sae_exact", 1)
@@ -577,9 +579,15 @@ def _both_paths(eng, x, tuning, loop=-1):
     return (idx_f, val_f), (idx_e, val_e), n_fb
 
 
-@pytest.mark.parametrize("loop", [-1, 0])
-@pytest.mark.parametrize("d_in,d_sae,k,n", [(128, 8192, 16, 600), (768, 24576, 32, 1100), (96, 4096, 64, 257), (104, 4096, 16, 300),
-                                            (768, 49152, 32, 700), (768, 3072, 32, 900), (128, 2048, 8, 300), (1280, 20480, 32, 500)])
+_FILTER_SHAPES = [(128, 8192, 16, 600), (768, 24576, 32, 1100), (96, 4096, 64, 257), (104, 4096, 16, 300),
+                  (768, 49152, 32, 700), (768, 3072, 32, 900), (128, 2048, 8, 300), (1280, 20480, 32, 500)]
+# every shape on the default and on the barrier-then-fetch loop; the two smallest with d_in % 64 == 0 also with the pipelined and
+# the full-line form forced (both legal there), so that each form of the shared K loop runs on fp16 operands
+_FILTER_CASES = ([s + (loop,) for loop in (-1, 0) for s in _FILTER_SHAPES] +
+                 [s + (loop,) for loop in (1, 2) for s in ((128, 2048, 8, 300), (768, 3072, 32, 900))])
+
+
+@pytest.mark.parametrize("d_in,d_sae,k,n,loop", _FILTER_CASES)
 def test_filtered_encoder_equals_exact_path(d_in, d_sae, k, n, loop, tuning):
     _, _, _, T = fresh(d_in, d_sae)
     T["b_enc"].mul_(20.0)                                                  # biases that matter

@@ -776,7 +776,9 @@ def test_bf16_results_do_not_depend_on_the_gemm_kernel_or_the_batch_size(tuning)
     an image's cache rows are the same bits at bs = 1 (v4 picked) and inside a 300-image batch (v7 picked)."""
     model, arch, _ = build("clip-vit-b32", torch.bfloat16)
     ref = None
-    for tile, loop in ((None, -1), (0, -1), (4, -1), (5, -1), (4, 0), (5, 0), (4, 2), (5, 2)):   # loop 0: barrier-then-fetch K loop, -1: pipelined, 2: full-line slabs
+    # loop -1: auto (every K of this model is whole 128-byte slabs: the full-line form, persistent where it pays), 0: barrier-then-
+    # fetch, 1: pipelined 64-byte slabs, 2: as auto
+    for tile, loop in ((None, -1), (0, -1), (4, -1), (5, -1), (4, 0), (5, 0), (4, 1), (5, 1), (4, 2), (5, 2)):
         tuning("reset")
         if tile is not None:
             tuning("gemm_tile", tile)

@@ -1,28 +1,23 @@
-// LDS-tiled MFMA GEMM for gfx950 with fused tap epilogues.
-//
-//   tile 128 x 128 per 256-thread workgroup (4 waves as 2 x 2, each wave 64 x 64 = 2 x 2 MFMA
-//   tiles of 32 x 32), K consumed in slabs of 128 BYTES per row (64 bf16 or 32 fp32), so the
-//   staging / LDS geometry is identical for both dtypes:
-//     - global -> registers: 16-byte chunks, 8 consecutive lanes cover one 128-byte row segment
-//     - registers -> LDS rows of 144 bytes (128 + one 16-byte access width of padding): the
-//       ds_read_b128 fragment reads (32 distinct rows per half-wave at one chunk column) are
-//       bank-conflict free (9*r mod 16 is a permutation over each 16-lane service group)
-//     - fragments: lane l reads row (l & 31), chunk 2*j + (l >> 5); for bf16 that IS the
-//       v_mfma_f32_32x32x16_bf16 operand (8 consecutive k per lane); for fp32 the 4 floats feed 4
-//       consecutive v_mfma_f32_32x32x2_f32 (A and B use the same k <-> lane-half assignment, so
-//       any consistent assignment gives the exact dot product)
-//     - double-buffered LDS, next slab's global loads issued before the MFMAs of the current one
-//   epilogue: accumulators -> per-wave LDS staging (reusing the operand buffers) -> each lane owns
-//   8 consecutive columns of a row -> bias / GELU / residual in fp32 -> 16-byte coalesced stores of
-//   every requested tap straight from the epilogue (the "fused hook-tap": caching an activation
-//   costs one HBM store, nothing is re-read).
-//   blockIdx -> tile mapping is XCD-aware: consecutive tiles along N (which share the A rows)
-//   are placed on the same XCD so the A slab is served from that XCD's L2.
+// The GEMMs of the ViT forward for gfx950, fp32 and bf16, with fused tap epilogues (bias / QKV split / residual add / activation;
+// "fused hook-tap": caching an activation costs one HBM store from the epilogue, nothing is re-read).  pv_launch_gemm() picks
+// (dispatch, pick_v7, launch_v7) among four kernel generations, all C[M][N] = A[M][K] . Bt[N][K]^T:
+//   gemm_kernel      128 x 128 tile, 256 threads, operands staged through registers into padded LDS rows, double-buffered.  Both
+//                    dtypes, any alignment, patch gather, [K][N] B operand: the kernel for whatever the others do not take.
+//                    (K in slabs of 128 BYTES per row, LDS rows of 144 bytes: 9 r mod 16 is a permutation over a 16-lane service
+//                    group, so the ds_read_b128 fragment reads are conflict-free; lane l reads row l & 31, chunk 2 j + (l >> 5): for
+//                    bf16 that IS the v_mfma_f32_32x32x16_bf16 operand, for fp32 the 4 floats feed 4 v_mfma_f32_32x32x2_f32.)
+//   gemm_kernel_v4   128 x 128 tile, operands DMA'd straight into a three-slot LDS ring, three workgroups per CU.
+//   gemm_kernel_v7   bf16, ONE 512-thread workgroup per CU, (64*MB) x 256 tile, template parameter LP = K-loop form:
+//                    0 barrier-then-fetch (patch gather, K tails), 1 software-pipelined 64-byte slabs, 2 full-line 128-byte slabs.
+//   gemm_kernel_v8   v7's full-line form made persistent: a workgroup walks its tiles, their K slabs one stream.
+// The K loops of v7 and v8 -- slot geometry, swizzles, step bodies, drivers -- and the XCD-aware tile order live in kloop.hpp,
+// shared with the SAE filter GEMM (sae_enc.hip); the kernels here keep their LDS objects, descriptors, piece sources and epilogues.
 #include <atomic>
 
 #include "gemm.hpp"
 
 #include <hip/hip_ext.h>
+#include "kloop.hpp"
 #include "prof.hpp"
 
 namespace {
@@ -304,6 +299,17 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x16 (&acc)
     }
 }
 
+// what the profiler books for a launch: its flops and its algorithmic bytes (each operand once, the outputs of its epilogue)
+struct GemmCost { double flops, bytes; };
+template <typename T>
+GemmCost gemm_cost(const GemmParams& p) {
+    const double mn = (double)p.M * p.N;
+    double outs = 1.0;                                              // BIAS / QKV: one M x N store
+    if (p.epi == PV_EPI_RESID) outs = 2.0 + (p.out0 ? 1.0 : 0.0);   // resid read + out1 (+ tap)
+    if (p.epi == PV_EPI_ACT) outs = 1.0 + (p.out0 ? 1.0 : 0.0);
+    return {2.0 * mn * p.K, ((double)p.M * p.K + (double)p.N * p.K + outs * mn) * DT<T>::kBytes};
+}
+
 constexpr int BKN_ROW = 528;         // [K][N]-layout B tile: 128 floats + 16 pad bytes per k row
 
 template <typename T, int AMODE, bool VEC, bool BKN = false>
@@ -320,10 +326,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
 
     // XCD-aware, bijective remap of the linear workgroup id (block b runs on XCD b % 8): each XCD
     // gets a contiguous run of tiles; tiles are ordered N-fastest so a run shares A rows.
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int swz = kloop::xcd_run(blockIdx.x, gridDim.x);
     const int ntn = (p.N + BN - 1) / BN;
     const int tile_m = swz / ntn, tile_n = swz - tile_m * ntn;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
@@ -448,7 +451,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
 //     applied on the DMA source address and on the fragment reads (conflict-free ds_read_b128)
 //   * epilogue staged through LDS in two 32-row halves per wave (34.8 KB <= the ring) 
 // ---------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* lds_ptr_t;      // destination of an LDS-DMA (buffer_load ... lds)
+using kloop::lds_ptr_t;
 constexpr int V4_SLAB = 64;                 // bytes of K per row per stage
 constexpr int V4_TILE = 128 * V4_SLAB;      // 8 KB per operand
 constexpr int V4_STAGE = 2 * V4_TILE;
@@ -468,21 +471,10 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel_v4(const GemmParams p) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    const int nwg = gridDim.x;
     const int bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    // tile order: column blocks of <= 8 N-tiles, M-major inside a block.  The B panel of a block
-    // (8 x 128 rows x K) stays resident in the XCD's 4 MB L2 while the M range streams past once per block,
-    // instead of the whole weight matrix being re-streamed every few M-tiles (PMC: L2-miss reads were 4x the
-    // algorithmic bytes with plain N-fastest order).
-    const int ntn = (p.N + BN - 1) / BN, ntm = (p.M + BM - 1) / BM;
-    const int nblk = (ntn + 7) / 8;
-    const int wblk = (ntn + nblk - 1) / nblk;
-    const int blk = swz / (ntm * wblk);
-    const int rem = swz - blk * (ntm * wblk);
-    const int wcur = min(wblk, ntn - blk * wblk);
-    const int tile_m = rem / wcur, tile_n = blk * wblk + (rem - tile_m * wcur);
+    const int swz = kloop::xcd_run(bid, gridDim.x);
+    int tile_m, tile_n;
+    kloop::TileOrder<BM, BN>(p.M, p.N).at(swz, tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     trace_stamp(p.trace, bid, 0);
 
@@ -499,7 +491,7 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel_v4(const GemmParams p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int row = (wave * 2 + j) * 16 + (lane >> 2);
-        const int kc = (lane & 3) ^ ((row >> 2) & 3);
+        const int kc = (lane & 3) ^ kloop::swz64(row);
         kcb[j] = kc * 16;
         offA[j] = (unsigned)(m0 + row) * (unsigned)p.lda * EB + kc * 16;
         offB[j] = (unsigned)(n0 + row) * (unsigned)p.ldb * EB + kc * 16;
@@ -538,7 +530,7 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel_v4(const GemmParams p) {
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
 
     const int l31 = lane & 31, half = lane >> 5;
-    const int sw = (l31 >> 2) & 3;
+    const int sw = kloop::swz64(l31);
     const int co0 = ((0 + half) ^ sw) * 16, co1 = ((2 + half) ^ sw) * 16;
     const int a_row = (wm * 64 + l31) * V4_SLAB;
     const int b_row = (wn * 64 + l31) * V4_SLAB;
@@ -684,12 +676,8 @@ template <typename T>
 int launch_v4(const GemmParams& p, hipStream_t stream) {
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
     {
-        constexpr double EBd = DT<T>::kBytes;
-        const double mn = (double)p.M * p.N;
-        double outs = 1.0;
-        if (p.epi == PV_EPI_RESID) outs = 2.0 + (p.out0 ? 1.0 : 0.0);
-        if (p.epi == PV_EPI_ACT) outs = 1.0 + (p.out0 ? 1.0 : 0.0);
-        ProfScope prof(PV_PROF_GEMM, stream, 2.0 * mn * p.K, ((double)p.M * p.K + (double)p.N * p.K + outs * mn) * EBd);
+        const GemmCost cost = gemm_cost<T>(p);
+        ProfScope prof(PV_PROF_GEMM, stream, cost.flops, cost.bytes);
         hipLaunchKernelGGL((gemm_kernel_v4<T>), dim3(ntm * ntn), dim3(256), 0, stream, p);
     }
     PV_LAUNCH_CHECK("gemm_kernel_v4");
@@ -706,12 +694,8 @@ int launch(const GemmParams& p, hipStream_t stream) {
         attr_done = true;
     }
     {
-        constexpr double EBd = DT<T>::kBytes;
-        const double mn = (double)p.M * p.N;
-        double outs = 1.0;                                   // BIAS / QKV: one M x N store
-        if (p.epi == PV_EPI_RESID) outs = 2.0 + (p.out0 ? 1.0 : 0.0);   // resid read + out1 (+ tap)
-        if (p.epi == PV_EPI_ACT) outs = 1.0 + (p.out0 ? 1.0 : 0.0);
-        ProfScope prof(PV_PROF_GEMM, stream, 2.0 * mn * p.K, ((double)p.M * p.K + (double)p.N * p.K + outs * mn) * EBd);
+        const GemmCost cost = gemm_cost<T>(p);
+        ProfScope prof(PV_PROF_GEMM, stream, cost.flops, cost.bytes);
         hipLaunchKernelGGL((gemm_kernel<T, AMODE, VEC, BKN>), dim3(ntm * ntn), dim3(256), GEMM_LDS, stream, p);
     }
     PV_LAUNCH_CHECK("gemm_kernel");
@@ -772,40 +756,30 @@ __device__ __forceinline__ void epi8_bf16(const float4& x0, const float4& x1, co
 template <typename T, int MB, int EPI, int ACT, int LP = 0>
 __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
     static_assert(sizeof(T) == 2, "v7 is the bf16 kernel");
-    constexpr int TM = 64 * MB;
-    constexpr int TN = 256;
-    constexpr int A_BYTES = TM * 64, B_BYTES = TN * 64, SLOT = A_BYTES + B_BYTES;
-    constexpr int NA = (4 * MB + 7) / 8;                  // A wave-instructions per wave per slab
-    constexpr bool PAD = (4 * MB) % 8 != 0;
-    static_assert(4 * SLOT + (PAD ? 8192 : 16) <= 160 * 1024, "one workgroup per CU");
-    // LP >= 2 (full-line form below): two slots of 128-byte rows in ring0 / ring1, the other objects shrink to stubs
+    using R64 = kloop::Ring64<MB>;
+    using R128 = kloop::Ring128<MB>;
+    constexpr int TM = 64 * MB, TN = 256, SLOT = R64::SLOT, NA = R64::NA;
+    static_assert(R128::SLOT == 2 * SLOT, "a full-line slot is two 64-byte-slab slots");
+    // the ring slots, one object each (kloop.hpp).  LP >= 2 (full-line form): two slots of 128-byte rows in ring0 / ring1, the other
+    // objects shrink to stubs
     __shared__ __attribute__((aligned(16))) unsigned char ring0[LP >= 2 ? 2 * SLOT : SLOT];
     __shared__ __attribute__((aligned(16))) unsigned char ring1[LP >= 2 ? 2 * SLOT : SLOT];
     __shared__ __attribute__((aligned(16))) unsigned char ring2[LP >= 2 ? 16 : SLOT];
     __shared__ __attribute__((aligned(16))) unsigned char ring3[LP >= 2 ? 16 : SLOT];
-    __shared__ __attribute__((aligned(16))) unsigned char pad[(PAD && LP < 2) ? 8192 : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char pad[LP < 2 ? R64::PAD_BYTES : 16];
     constexpr int EB = DT<T>::kBytes;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    const int nwg = gridDim.x;
     const int bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    const int ntn = (p.N + TN - 1) / TN, ntm = (p.M + TM - 1) / TM;
-    const int nblk = (ntn + 7) / 8;
-    const int wblk = (ntn + nblk - 1) / nblk;
-    const int blk = swz / (ntm * wblk);
-    const int rem = swz - blk * (ntm * wblk);
-    const int wcur = min(wblk, ntn - blk * wblk);
-    const int tile_m = rem / wcur, tile_n = blk * wblk + (rem - tile_m * wcur);
+    const int swz = kloop::xcd_run(bid, gridDim.x);
+    int tile_m, tile_n;
+    kloop::TileOrder<TM, TN>(p.M, p.N).at(swz, tile_m, tile_n);
     const int m0 = tile_m * TM, n0 = tile_n * TN;
     trace_stamp(p.trace, bid, 0);
 
     const unsigned Kb = (unsigned)p.K * EB;
-    const int nk = (int)((Kb + 63) / 64);
-    const bool ktail = (Kb % 64) != 0;
     // PATCH A operand (patch size 32, bf16): the 64 bytes of K that slab kt covers are ONE contiguous run of the
     // NCHW image -- channel kt / 32, patch row kt % 32 -- so the im2col-free gather is only a different row base and
     // slab offset for the same DMA (patch_embedding.py:26-32)
@@ -814,88 +788,12 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
                                   : (unsigned)p.M * (unsigned)p.lda * EB;
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.A), 0, (int)a_span, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void*>(p.Bt), 0, (int)((unsigned)p.N * (unsigned)p.ldb * EB), 0x00020000);
-
-    // a wave-instruction moves 16 rows x 64 B; A has 4*MB of them per slab (instruction j*8 + wave), B has 16
-    unsigned offA[NA], kcA[NA], offB[2], kcB[2];
-    bool realA[NA];
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-        const int ia = j * 8 + wave;
-        realA[j] = ia < 4 * MB;
-        const int row = ia * 16 + (lane >> 2);
-        const int kc = (lane & 3) ^ ((row >> 2) & 3);
-        kcA[j] = kc * 16;
-        if (patch) {
-            const int gm = m0 + row, np = p.pG * p.pG;
-            const int b = gm / np, pidx = gm - b * np;
-            const int py = pidx / p.pG, px = pidx - py * p.pG;
-            offA[j] = (unsigned)(((b * p.pC) * p.pS + py * p.pP) * p.pS + px * p.pP) * EB + kc * 16;      // image b >= B: past the range -> 0
-        } else {
-            offA[j] = (unsigned)(m0 + row) * (unsigned)p.lda * EB + kc * 16;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int row = (j * 8 + wave) * 16 + (lane >> 2);
-        const int kc = (lane & 3) ^ ((row >> 2) & 3);
-        kcB[j] = kc * 16;
-        offB[j] = (unsigned)(n0 + row) * (unsigned)p.ldb * EB + kc * 16;
-    }
-    auto issue = [&](int kt, unsigned char* slot) {
-        const unsigned kbase = (unsigned)kt * 64;
-        bool dead = (kt >= nk);
-#ifdef PV_TUNING
-        dead |= (((p.dbg & 1) != 0) & (kt >= 3));
-#endif
-        // (selects only: a branch around an LDS-DMA makes hipcc drain the queue before the next ds_read)
-        const unsigned kbaseA = patch ? (unsigned)((kt >> 5) * p.pS * p.pS + (kt & 31) * p.pS) * EB : kbase;
-#pragma unroll
-        for (int j = 0; j < NA; ++j) {
-            unsigned o = offA[j] + kbaseA;
-            o = (dead | !realA[j] | (ktail & (kbase + kcA[j] >= Kb))) ? 0xffffff00u : o;
-            unsigned char* dst = slot + (j * 8 + wave) * 1024;
-            if constexpr (PAD) { if (j == NA - 1) dst = realA[j] ? dst : pad + wave * 1024; }
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)dst, 16, o, 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            unsigned o = offB[j] + kbase;
-            o = (dead | (ktail & (kbase + kcB[j] >= Kb))) ? 0xffffff00u : o;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(slot + A_BYTES + (j * 8 + wave) * 1024), 16, o, 0, 0, 0);
-        }
-    };
+        const_cast<void*>(p.Bt), 0, (int)((unsigned)p.N * (unsigned)p.ldb * EB), 0x00020000);      // (rows >= N: past the range -> 0)
+    const unsigned ldaB = (unsigned)p.lda * EB, ldbB = (unsigned)p.ldb * EB;
 
     f32x16 acc[MB][2];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-
+    kloop::zero(acc);
     const int l31 = lane & 31, half = lane >> 5;
-    const int sw = (l31 >> 2) & 3;
-    const int co0 = ((0 + half) ^ sw) * 16, co1 = ((2 + half) ^ sw) * 16;
-    const int a_row = (wm * 32 * MB + l31) * 64;
-    const int b_row = A_BYTES + (wn * 64 + l31) * 64;
-    auto compute = [&](const unsigned char* slot) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int co = j == 0 ? co0 : co1;
-            uint4 a[MB], b[2];
-#pragma unroll
-            for (int mi = 0; mi < MB; ++mi) a[mi] = *reinterpret_cast<const uint4*>(slot + a_row + mi * 2048 + co);
-            b[0] = *reinterpret_cast<const uint4*>(slot + b_row + co);
-            b[1] = *reinterpret_cast<const uint4*>(slot + b_row + 2048 + co);
-#pragma unroll
-            for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                        __builtin_bit_cast(bf16x8, a[mi]), __builtin_bit_cast(bf16x8, b[ni]), acc[mi][ni], 0, 0, 0);
-        }
-    };
 
     // epilogue operands in flight before the K loop (see v4): bias chunk + residual rows of block 0.
     // The launcher guarantees vec_out and N % 8 == 0: whole 8-element chunks only.
@@ -930,212 +828,78 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
     }
     PV_V7_FETCH_RES(0)
 
-    // step kt: slab kt must have landed -- the 2 * (NA + 2) DMA instructions of slabs kt+1, kt+2 may stay in flight
-    constexpr int NPIECE = NA + 2;
-    static_assert(2 * NPIECE <= 15, "vmcnt immediate below uses the low 4 bits only");
-#define PV_V7_SYNC() __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * NPIECE)); __builtin_amdgcn_s_barrier();
-#define PV_V7_STEP(KT, CUR, NXT3)                               \
-    PV_V7_SYNC()                                                \
-    issue((KT) + 3, NXT3);                                      \
-    compute(CUR);
-
+    // the K loop (kloop.hpp); what is written here is where each form's pieces come from
     if constexpr (LP == 0) {
-        issue(0, ring0);
-        issue(1, ring1);
-        issue(2, ring2);
-        int kt = 0;
-        for (; kt + 4 <= nk; kt += 4) {
-            PV_V7_STEP(kt, ring0, ring3)
-            PV_V7_STEP(kt + 1, ring1, ring0)
-            PV_V7_STEP(kt + 2, ring2, ring1)
-            PV_V7_STEP(kt + 3, ring3, ring2)
+        // any A operand, any K: per piece a per-lane base, a uniform slab term and the K-tail test
+        const R64 g(lane, wave, pad);
+        const int nk = (int)((Kb + 63) / 64);
+        const bool ktail = (Kb % 64) != 0;
+        unsigned offA[NA], kcA[NA], offB[2], kcB[2];
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            const int row = g.piece_row(lane, j);
+            kcA[j] = R64::piece_col(lane, row);
+            if (patch) {
+                const int gm = m0 + row, np = p.pG * p.pG;
+                const int b = gm / np, pidx = gm - b * np;
+                const int py = pidx / p.pG, px = pidx - py * p.pG;
+                offA[j] = (unsigned)(((b * p.pC) * p.pS + py * p.pP) * p.pS + px * p.pP) * EB + kcA[j];      // image b >= B: past the range -> 0
+            } else {
+                offA[j] = (unsigned)(m0 + row) * ldaB + kcA[j];
+            }
         }
-        if (kt < nk) { PV_V7_STEP(kt, ring0, ring3) }
-        if (kt + 1 < nk) { PV_V7_STEP(kt + 1, ring1, ring0) }
-        if (kt + 2 < nk) { PV_V7_STEP(kt + 2, ring2, ring1) }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int row = g.piece_row(lane, j);
+            kcB[j] = R64::piece_col(lane, row);
+            offB[j] = (unsigned)(n0 + row) * ldbB + kcB[j];
+        }
+        auto issue = [&](int kt, unsigned char* slot) {
+            const unsigned kbase = (unsigned)kt * 64;
+            bool dead = (kt >= nk);
+#ifdef PV_TUNING
+            dead |= (((p.dbg & 1) != 0) & (kt >= 3));
+#endif
+            const unsigned kbaseA = patch ? (unsigned)((kt >> 5) * p.pS * p.pS + (kt & 31) * p.pS) * EB : kbase;
+#pragma unroll
+            for (int j = 0; j < NA; ++j)
+                g.issue(rsA, rsB, slot, j, (dead | !g.real_a(j) | (ktail & (kbase + kcA[j] >= Kb))) ? kloop::DEAD : offA[j] + kbaseA);
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                g.issue(rsA, rsB, slot, NA + j, (dead | (ktail & (kbase + kcB[j] >= Kb))) ? kloop::DEAD : offB[j] + kbase);
+        };
+        KLOOP_RUN_FETCH_AFTER_BARRIER(kloop::Bf16, acc, g, ring0, ring1, ring2, ring3, nk, issue);
     } else if constexpr (LP == 1) {
-        // Software-pipelined form.  The loop above has every wave arrive at the slab's barrier with empty fragment
-        // registers: both waves of a SIMD then issue their DMA pieces and their first ds_reads and sit out the LDS
-        // latency with the matrix pipe idle.  Here the fragments of a half-slab are fetched while the previous
-        // half-slab is multiplied (each A fragment is refilled right behind the two MFMAs that consumed it), the
-        // barrier of slab s+1 sits in the MIDDLE of step s (between its two halves: by then every read of slab s has
-        // been issued, and the second half's operands are already in registers), and the DMA pieces of slab s+4 go
-        // out one per MFMA pair during the second half, into the slot the barrier has just freed.
-        //   ring depth as before: at the barrier of slab s+1 the pieces of slabs s+2 and s+3 stay in flight.
-        // (plain A operand, whole 64-byte slabs only -- the launcher keeps the loop above for the patch gather and
-        // for a K tail: a piece's source offset is then one per-lane base + a uniform term, two VALU per piece)
-        const unsigned pA0 = (unsigned)(m0 + wave * 16 + (lane >> 2)) * (unsigned)p.lda * EB + (((lane & 3) ^ ((lane >> 4) & 3)) * 16);
-        const unsigned pB0 = (unsigned)(n0 + wave * 16 + (lane >> 2)) * (unsigned)p.ldb * EB + (((lane & 3) ^ ((lane >> 4) & 3)) * 16);
-        const unsigned strideA = 128u * (unsigned)p.lda * EB, strideB = 128u * (unsigned)p.ldb * EB;
-        auto issue_piece = [&](int kt, unsigned char* slot, int j) {
+        // plain A operand, whole 64-byte slabs only (the launcher keeps LP = 0 for the patch gather and for a K tail): a piece's
+        // source offset is one per-lane base + a uniform term, two VALU per piece
+        const R64 g(lane, wave, pad);
+        const int nk = (int)((Kb + 63) / 64);
+        const int row0 = g.piece_row(lane, 0);
+        const unsigned pA0 = (unsigned)(m0 + row0) * ldaB + R64::piece_col(lane, row0);
+        const unsigned pB0 = (unsigned)(n0 + row0) * ldbB + R64::piece_col(lane, row0);
+        const unsigned strideA = R64::PIECE_STRIDE * ldaB, strideB = R64::PIECE_STRIDE * ldbB;
+        auto src = [&](int kt, int j) -> unsigned {
             const unsigned kbase = (unsigned)kt * 64;
             const bool dead = (kt >= nk);
-            if (j < NA) {
-                const bool off = dead | ((j * 8 + wave) >= 4 * MB);                  // uniform
-                const unsigned o = off ? 0xffffff00u : pA0 + ((unsigned)j * strideA + kbase);
-                unsigned char* dst = slot + (j * 8 + wave) * 1024;
-                if constexpr (PAD) { if (j == NA - 1) dst = (j * 8 + wave) < 4 * MB ? dst : pad + wave * 1024; }
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)dst, 16, o, 0, 0, 0);
-            } else {
-                const int jb = j - NA;
-                const unsigned o = dead ? 0xffffff00u : pB0 + ((unsigned)jb * strideB + kbase);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(slot + A_BYTES + (jb * 8 + wave) * 1024), 16, o, 0, 0, 0);
-            }
+            if (j < NA) return (dead | !g.real_a(j)) ? kloop::DEAD : pA0 + ((unsigned)j * strideA + kbase);
+            return dead ? kloop::DEAD : pB0 + ((unsigned)(j - NA) * strideB + kbase);
         };
-        auto issue_all = [&](int kt, unsigned char* slot) {
-#pragma unroll
-            for (int j = 0; j < NPIECE; ++j) issue_piece(kt, slot, j);
-        };
-        auto rdA = [&](const unsigned char* slot, int h, int mi) {
-            return *reinterpret_cast<const uint4*>(slot + a_row + mi * 2048 + (h == 0 ? co0 : co1));
-        };
-        auto rdB = [&](const unsigned char* slot, int h, int ni) {
-            return *reinterpret_cast<const uint4*>(slot + b_row + ni * 2048 + (h == 0 ? co0 : co1));
-        };
-        static_assert(3 * NPIECE <= 15 && NPIECE <= MB, "prologue vmcnt immediate; one DMA piece per MFMA pair");
-        constexpr int BPOS = MB >= 4 ? 1 : 0;           // which MFMA pair the next half's B fragments are fetched behind
-        uint4 fa[MB], fb0[2], fb1[2];
-        // the issue order below is the schedule: MFMA pair | DMA piece + fragment refill | MFMA pair | ... (left to itself
-        // hipcc sinks the refills to the end of the half-slab and waits for them right behind the barrier)
-#define PV_V7_PIN() __builtin_amdgcn_sched_barrier(0)
-#define PV_V7_PIN2() __builtin_amdgcn_sched_barrier(0)
-#define PV_V7_PAIR(MI, FB)                                                                                   \
-        _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                     \
-            acc[MI][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                                           \
-                __builtin_bit_cast(bf16x8, fa[MI]), __builtin_bit_cast(bf16x8, FB[ni]), acc[MI][ni], 0, 0, 0);
-        // step KT: slab KT in CUR (visible), slab KT+1 in NXT; fa / fb0 hold the first half of slab KT
-#define PV_V7_PSTEP(KT, CUR, NXT)                                                                            \
-        _Pragma("unroll") for (int mi = 0; mi < MB; ++mi) {                                                  \
-            PV_V7_PAIR(mi, fb0)                                                                              \
-            PV_V7_PIN2();                                                                                    \
-            fa[mi] = rdA(CUR, 1, mi);                                                                        \
-            if (mi == BPOS) { fb1[0] = rdB(CUR, 1, 0); fb1[1] = rdB(CUR, 1, 1); }                            \
-            PV_V7_PIN();                                                                                     \
-        }                                                                                                    \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-        __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * NPIECE));                                                   \
-        __builtin_amdgcn_s_barrier();                                                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-        _Pragma("unroll") for (int mi = 0; mi < MB; ++mi) {                                                  \
-            PV_V7_PAIR(mi, fb1)                                                                              \
-            PV_V7_PIN2();                                                                                    \
-            fa[mi] = rdA(NXT, 0, mi);                                                                        \
-            if (mi == BPOS) { fb0[0] = rdB(NXT, 0, 0); fb0[1] = rdB(NXT, 0, 1); }                            \
-            if (mi < NPIECE) issue_piece((KT) + 4, CUR, mi);                                                 \
-            PV_V7_PIN();                                                                                     \
-        }
-        issue_all(0, ring0);
-        issue_all(1, ring1);
-        issue_all(2, ring2);
-        issue_all(3, ring3);
-        __builtin_amdgcn_s_waitcnt(0x0F70 | (3 * NPIECE));
-        __builtin_amdgcn_s_barrier();
-#pragma unroll
-        for (int mi = 0; mi < MB; ++mi) fa[mi] = rdA(ring0, 0, mi);
-        fb0[0] = rdB(ring0, 0, 0); fb0[1] = rdB(ring0, 0, 1);
-        int kt = 0;
-        for (; kt + 4 <= nk; kt += 4) {
-            PV_V7_PSTEP(kt, ring0, ring1)
-            PV_V7_PSTEP(kt + 1, ring1, ring2)
-            PV_V7_PSTEP(kt + 2, ring2, ring3)
-            PV_V7_PSTEP(kt + 3, ring3, ring0)
-        }
-        if (kt < nk) { PV_V7_PSTEP(kt, ring0, ring1) }
-        if (kt + 1 < nk) { PV_V7_PSTEP(kt + 1, ring1, ring2) }
-        if (kt + 2 < nk) { PV_V7_PSTEP(kt + 2, ring2, ring3) }
-#undef PV_V7_PSTEP
-#undef PV_V7_PAIR
-#undef PV_V7_PIN
-#undef PV_V7_PIN2
+        KLOOP_RUN_PIPELINED64(kloop::Bf16, MB, acc, g, rsA, rsB, ring0, ring1, ring2, ring3, nk, src);
     } else {
-        // Full-line form (LP == 2): K slabs of 128 BYTES per row, i.e. whole cache lines -- a DMA piece (1 KiB) is 8 rows x 128 B
-        // = 8 lines instead of 16 half lines (the 64-byte slabs above pull every operand line through the L1 twice, 1 us
-        // apart, and the texture addresser is busy 55-79 % of the launch: profiles/r02_notes.md).  Two 72 KB slots; the
-        // software pipeline of LP == 1 on four 16-element k-steps per slab: the barrier of slab s+1 sits before the LAST k-step
-        // of slab s (every read of slab s has been issued by then), the pieces of slab s+2 go out behind the MFMA pairs of
-        // that last k-step (into the slot the barrier freed) and of the next slab's first k-step.  One slab of prefetch
-        // distance (the slot it lands in is read until the barrier), so the wait before the barrier is vmcnt(0).
-        //   LDS row = 128 B = 8 chunks; chunk c of row r at position c ^ ((r >> 1) & 7): the 16 rows of a ds_read_b128 lane group
-        //   (8 even, 8 odd) then cover all 64 banks.
-        constexpr int A2 = TM * 128;                                   // bytes of the A part of a slot
-        constexpr int NP2 = MB + 4;                                    // pieces per wave per slab: MB of A, 4 of B
-        static_assert(MB >= 4, "four B pieces ride on the first k-step's MFMA pairs");
-        const int prow = lane >> 3;                                    // row of the piece this lane fetches
-        const int psw = ((lane >> 4) + 4 * (wave & 1)) & 7;            // (row >> 1) & 7 of that row (row = (j*8 + wave)*8 + prow)
-        const unsigned pcol = (unsigned)(((lane & 7) ^ psw) * 16);
-        const unsigned pA0 = (unsigned)(m0 + wave * 8 + prow) * (unsigned)p.lda * EB + pcol;
-        const unsigned pB0 = (unsigned)(n0 + wave * 8 + prow) * (unsigned)p.ldb * EB + pcol;
-        const unsigned strideA = 64u * (unsigned)p.lda * EB, strideB = 64u * (unsigned)p.ldb * EB;
+        // plain A operand, whole 128-byte slabs only
+        const R128 g(lane, wave);
         const int nk2 = (int)(Kb / 128);
-        auto issue_piece2 = [&](int kt, unsigned char* slot, int j) {
+        const unsigned pA0 = (unsigned)(m0 + g.piece_row(lane)) * ldaB + g.piece_col(lane);
+        const unsigned pB0 = (unsigned)(n0 + g.piece_row(lane)) * ldbB + g.piece_col(lane);
+        const unsigned strideA = R128::PIECE_STRIDE * ldaB, strideB = R128::PIECE_STRIDE * ldbB;
+        auto src = [&](int kt, int j) -> unsigned {
             const unsigned kbase = (unsigned)kt * 128;
             const bool dead = (kt >= nk2);
-            if (j < MB) {
-                const unsigned o = dead ? 0xffffff00u : pA0 + ((unsigned)j * strideA + kbase);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)(slot + (j * 8 + wave) * 1024), 16, o, 0, 0, 0);
-            } else {
-                const int jb = j - MB;
-                const unsigned o = dead ? 0xffffff00u : pB0 + ((unsigned)jb * strideB + kbase);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(slot + A2 + (jb * 8 + wave) * 1024), 16, o, 0, 0, 0);
-            }
+            if (j < MB) return dead ? kloop::DEAD : pA0 + ((unsigned)j * strideA + kbase);
+            return dead ? kloop::DEAD : pB0 + ((unsigned)(j - MB) * strideB + kbase);
         };
-        const int fsw = (l31 >> 1) & 7;
-        const int a_row2 = (wm * 32 * MB + l31) * 128, b_row2 = A2 + (wn * 64 + l31) * 128;
-        int fco[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) fco[h] = ((2 * h + half) ^ fsw) * 16;
-        auto rdA2 = [&](const unsigned char* slot, int h, int mi) {
-            return *reinterpret_cast<const uint4*>(slot + a_row2 + mi * 4096 + fco[h]);
-        };
-        auto rdB2 = [&](const unsigned char* slot, int h, int ni) {
-            return *reinterpret_cast<const uint4*>(slot + b_row2 + ni * 4096 + fco[h]);
-        };
-        uint4 fa[MB], fb[2][2];
-#define PV_V7_PAIR2(MI, H)                                                                                    \
-        _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                      \
-            acc[MI][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                                            \
-                __builtin_bit_cast(bf16x8, fa[MI]), __builtin_bit_cast(bf16x8, fb[(H) & 1][ni]), acc[MI][ni], 0, 0, 0); \
-        __builtin_amdgcn_sched_barrier(0);
-        // slab KT in CUR (visible), slab KT+1 arriving in NXT; fa / fb[0] hold k-step 0 of slab KT
-#define PV_V7_FSTEP(KT, CUR, NXT)                                                                             \
-        _Pragma("unroll") for (int h = 0; h < 4; ++h) {                                                       \
-            if (h == 3) {                                                                                     \
-                __builtin_amdgcn_s_waitcnt(0x0F70);                                                           \
-                __builtin_amdgcn_s_barrier();                                                                 \
-                __builtin_amdgcn_sched_barrier(0);                                                            \
-            }                                                                                                 \
-            _Pragma("unroll") for (int mi = 0; mi < MB; ++mi) {                                               \
-                PV_V7_PAIR2(mi, h)                                                                            \
-                fa[mi] = h < 3 ? rdA2(CUR, h < 3 ? h + 1 : 0, mi) : rdA2(NXT, 0, mi);                         \
-                if (mi == 1) {                                                                                \
-                    fb[(h + 1) & 1][0] = h < 3 ? rdB2(CUR, h < 3 ? h + 1 : 0, 0) : rdB2(NXT, 0, 0);           \
-                    fb[(h + 1) & 1][1] = h < 3 ? rdB2(CUR, h < 3 ? h + 1 : 0, 1) : rdB2(NXT, 0, 1);           \
-                }                                                                                             \
-                if (h == 3) issue_piece2((KT) + 2, CUR, mi);                                                  \
-                if (h == 0 && mi < 4) issue_piece2((KT) + 1, NXT, MB + mi);                                   \
-                __builtin_amdgcn_sched_barrier(0);                                                            \
-            }                                                                                                 \
-        }
-#pragma unroll
-        for (int j = 0; j < NP2; ++j) issue_piece2(0, ring0, j);
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        __builtin_amdgcn_s_barrier();
-#pragma unroll
-        for (int j = 0; j < MB; ++j) issue_piece2(1, ring1, j);      // (the B pieces of slab 1 ride on step 0's first k-step)
-#pragma unroll
-        for (int mi = 0; mi < MB; ++mi) fa[mi] = rdA2(ring0, 0, mi);
-        fb[0][0] = rdB2(ring0, 0, 0); fb[0][1] = rdB2(ring0, 0, 1);
-        int kt = 0;
-        for (; kt + 2 <= nk2; kt += 2) {
-            PV_V7_FSTEP(kt, ring0, ring1)
-            PV_V7_FSTEP(kt + 1, ring1, ring0)
-        }
-        if (kt < nk2) { PV_V7_FSTEP(kt, ring0, ring1) }
-#undef PV_V7_FSTEP
-#undef PV_V7_PAIR2
+        KLOOP_RUN_FULL_LINE(kloop::Bf16, MB, acc, g, rsA, rsB, ring0, ring1, nk2, src);
     }
-#undef PV_V7_STEP
-#undef PV_V7_SYNC
     __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0): drain the off-the-end prefetches
     __syncthreads();
     trace_stamp(p.trace, bid, 1);
@@ -1211,14 +975,14 @@ __device__ __forceinline__ int lane_id_here() {
 template <typename T, int MB, int EPI, int ACT>
 __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, const int ntiles, const int stagger) {
     static_assert(sizeof(T) == 2, "v8 is a bf16 kernel");
+    using R128 = kloop::Ring128<MB, true>;
     constexpr int TM = 64 * MB;
     constexpr int TN = 256;
-    constexpr int A2 = TM * 128, B2 = TN * 128, SLOT2 = A2 + B2;      // one slot: (TM + TN) rows x 128 bytes of K
+    constexpr int A2 = R128::A_BYTES, B2 = R128::B_BYTES;             // one slot: (TM + TN) rows x 128 bytes of K
     constexpr int STAGE = 8 * 2048;                                   // epilogue transposition: 8 rows x 64 fp32 per wave
-    static_assert(MB >= 4, "four B pieces ride on the first k-step's MFMA pairs");
-    static_assert(2 * SLOT2 + STAGE <= 160 * 1024, "one workgroup per CU");
-    // four LDS objects, the A / B part of either slot (hipcc's alias scopes are per object -- gemm_kernel_v4: the ds_reads of one slot
-    // must not be taken to alias the DMA writes in flight to the other)
+    static_assert(2 * (A2 + B2) + STAGE <= 160 * 1024, "one workgroup per CU");
+    // four LDS objects, the A / B part of either slot (one object per slot, kloop.hpp: the ds_reads of one slot must not be taken
+    // to alias the DMA writes in flight to the other)
     __shared__ __attribute__((aligned(16))) unsigned char ringA0[A2];
     __shared__ __attribute__((aligned(16))) unsigned char ringA1[A2];
     __shared__ __attribute__((aligned(16))) unsigned char ringB0[B2];
@@ -1229,20 +993,13 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, con
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    const int l31 = lane & 31, half = lane >> 5;
-    const int ntn = (p.N + TN - 1) / TN, ntm = (p.M + TM - 1) / TM;
-    const int nblk = (ntn + 7) / 8;
-    const int wblk = (ntn + nblk - 1) / nblk;
     // virtual block id -> tile origin (v7's mapping with the virtual grid size: bid and bid + k * gridDim.x sit on the same XCD)
+    const kloop::TileOrder<TM, TN> order(p.M, p.N);
     auto tile_of = [&](int vb, int& m0, int& n0) {
-        const int q = ntiles >> 3, r = ntiles & 7, xcd = vb & 7;
-        const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-        const int blk = swz / (ntm * wblk);
-        const int rem = swz - blk * (ntm * wblk);
-        const int wcur = min(wblk, ntn - blk * wblk);
-        const int tile_m = rem / wcur;
+        int tile_m, tile_n;
+        order.at(kloop::xcd_run(vb, ntiles), tile_m, tile_n);
         m0 = tile_m * TM;
-        n0 = (blk * wblk + (rem - tile_m * wcur)) * TN;
+        n0 = tile_n * TN;
     };
     const unsigned Kb = (unsigned)p.K * EB;
     const int nk2 = (int)(Kb / 128);
@@ -1250,77 +1007,28 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, con
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.A), 0, (int)((unsigned)p.M * ldaB), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Bt), 0, (int)((unsigned)p.N * ldbB), 0x00020000);
 
-    // DMA pieces (1 KiB = 8 rows x 128 B): per-lane part of the source offset; the tile's origin and the slab are uniform terms
-    const int prow = lane >> 3;
-    const int psw = ((lane >> 4) + 4 * (wave & 1)) & 7;            // (row >> 1) & 7 of the piece row this lane fetches
-    const unsigned pcol = (unsigned)(((lane & 7) ^ psw) * 16);
-    const unsigned lpA = (unsigned)(wave * 8 + prow) * ldaB + pcol;
-    const unsigned lpB = (unsigned)(wave * 8 + prow) * ldbB + pcol;
-    const unsigned strideA = 64u * ldaB, strideB = 64u * ldbB;
+    // DMA pieces: per-lane part of the source offset; the tile's origin and the slab are uniform terms
+    const R128 g(lane, wave);
+    const unsigned lpA = (unsigned)g.piece_row(lane) * ldaB + g.piece_col(lane);
+    const unsigned lpB = (unsigned)g.piece_row(lane) * ldbB + g.piece_col(lane);
+    const unsigned strideA = R128::PIECE_STRIDE * ldaB, strideB = R128::PIECE_STRIDE * ldbB;
     unsigned uA, uB, uAn = 0, uBn = 0;                              // this tile's / the next tile's uniform origin terms
     bool dead_n = true;
-    // piece j of slab s (s >= nk2: slab s - nk2 of the NEXT tile) into `slot`
-    auto issue_piece = [&](int s, unsigned char* slotA, unsigned char* slotB, int j) {
+    // piece j of slab s; s >= nk2: slab s - nk2 of the NEXT tile (selects on a uniform condition)
+    auto src = [&](int s, int j) -> unsigned {
         const bool nx = s >= nk2;
         const unsigned sb = (unsigned)(nx ? s - nk2 : s) * 128u;
         const bool dead = nx & dead_n;
-        if (j < MB) {
-            unsigned o = lpA + ((nx ? uAn : uA) + (unsigned)j * strideA + sb);
-            o = dead ? 0xffffff00u : o;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)(slotA + (j * 8 + wave) * 1024), 16, o, 0, 0, 0);
-        } else {
-            const int jb = j - MB;
-            unsigned o = lpB + ((nx ? uBn : uB) + (unsigned)jb * strideB + sb);
-            o = dead ? 0xffffff00u : o;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(slotB + (jb * 8 + wave) * 1024), 16, o, 0, 0, 0);
-        }
-    };
-    const int fsw = (l31 >> 1) & 7;
-    const int a_row2 = (wm * 32 * MB + l31) * 128, b_row2 = (wn * 64 + l31) * 128;
-    int fco[4];
-#pragma unroll
-    for (int h = 0; h < 4; ++h) fco[h] = ((2 * h + half) ^ fsw) * 16;
-    auto rdA2 = [&](const unsigned char* slotA, int h, int mi) {
-        return *reinterpret_cast<const uint4*>(slotA + a_row2 + mi * 4096 + fco[h]);
-    };
-    auto rdB2 = [&](const unsigned char* slotB, int h, int ni) {
-        return *reinterpret_cast<const uint4*>(slotB + b_row2 + ni * 4096 + fco[h]);
+        const unsigned o = j < MB ? lpA + ((nx ? uAn : uA) + (unsigned)j * strideA + sb)
+                                  : lpB + ((nx ? uBn : uB) + (unsigned)(j - MB) * strideB + sb);
+        return dead ? kloop::DEAD : o;
     };
 
     f32x16 acc[MB][2];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-#define PV_V8_PAIR(MI, H)                                                                                     \
-    _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                          \
-        acc[MI][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                                                \
-            __builtin_bit_cast(bf16x8, fa[MI]), __builtin_bit_cast(bf16x8, fb[(H) & 1][ni]), acc[MI][ni], 0, 0, 0); \
-    __builtin_amdgcn_sched_barrier(0);
-    // slab KT in CUR (visible), slab KT+1 arriving in NXT; fa / fb[0] hold k-step 0 of slab KT (v7's PV_V7_FSTEP)
-#define PV_V8_FSTEP(KT, CA, CB, NA, NB)                                                                       \
-    _Pragma("unroll") for (int h = 0; h < 4; ++h) {                                                           \
-        if (h == 3) {                                                                                         \
-            __builtin_amdgcn_s_waitcnt(0x0F70);                                                               \
-            __builtin_amdgcn_s_barrier();                                                                     \
-            __builtin_amdgcn_sched_barrier(0);                                                                \
-        }                                                                                                     \
-        _Pragma("unroll") for (int mi = 0; mi < MB; ++mi) {                                                   \
-            PV_V8_PAIR(mi, h)                                                                                 \
-            fa[mi] = h < 3 ? rdA2(CA, h < 3 ? h + 1 : 0, mi) : rdA2(NA, 0, mi);                               \
-            if (mi == 1) {                                                                                    \
-                fb[(h + 1) & 1][0] = h < 3 ? rdB2(CB, h < 3 ? h + 1 : 0, 0) : rdB2(NB, 0, 0);                 \
-                fb[(h + 1) & 1][1] = h < 3 ? rdB2(CB, h < 3 ? h + 1 : 0, 1) : rdB2(NB, 0, 1);                 \
-            }                                                                                                 \
-            if (h == 3) issue_piece((KT) + 2, CA, CB, mi);                                                    \
-            if (h == 0 && mi < 4) issue_piece((KT) + 1, NA, NB, MB + mi);                                     \
-            __builtin_amdgcn_sched_barrier(0);                                                                \
-        }                                                                                                     \
-    }
-#define PV_V8_EVEN(KT) PV_V8_FSTEP(KT, ringA0, ringB0, ringA1, ringB1)
-#define PV_V8_ODD(KT) PV_V8_FSTEP(KT, ringA1, ringB1, ringA0, ringB0)
+    kloop::zero(acc);
+    // the tile's slabs alternate between the slots: even ones in ringA0 / ringB0
+#define PV_V8_EVEN(KT) kloop::step_full_line<kloop::Bf16>(acc, fa, fb, g, rsA, rsB, KT, ringA0, ringB0, ringA1, ringB1, src);
+#define PV_V8_ODD(KT) kloop::step_full_line<kloop::Bf16>(acc, fa, fb, g, rsA, rsB, KT, ringA1, ringB1, ringA0, ringB0, src);
 
     int vb = blockIdx.x;
     int m0, n0;
@@ -1332,13 +1040,8 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, con
         for (int i = 0; i < k; ++i) __builtin_amdgcn_s_sleep(127);
     }
     trace_stamp(p.trace, vb, 0);
-    // the stream's head: slab 0 of the first tile entirely, the A pieces of its slab 1, k-step 0's fragments
-#pragma unroll
-    for (int j = 0; j < (MB + 4); ++j) issue_piece(0, ringA0, ringB0, j);
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int j = 0; j < MB; ++j) issue_piece(1, ringA1, ringB1, j);
+    // the stream's head: slab 0 of the first tile entirely, the A pieces of its slab 1
+    g.prologue(rsA, rsB, ringA0, ringB0, ringA1, ringB1, src);
 
     for (;;) {
         const int vbn = vb + (int)gridDim.x;
@@ -1381,9 +1084,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, con
         // k-step 0's fragments of the tile's first slab (visible since the last barrier of the previous tile's loop; that loop's
         // last refills fetched the same values, but carrying 36 registers across the epilogue costs the loop body spills)
         uint4 fa[MB], fb[2][2];
-#pragma unroll
-        for (int mi = 0; mi < MB; ++mi) fa[mi] = rdA2(ringA0, 0, mi);
-        fb[0][0] = rdB2(ringB0, 0, 0); fb[0][1] = rdB2(ringB0, 0, 1);
+        g.first_fragments(fa, fb, ringA0, ringB0);
         int kt = 0;
         do {                                                       // (nk2 >= 2 and even: the launcher's condition)
             PV_V8_EVEN(kt)
@@ -1442,19 +1143,12 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, con
 #undef PV_V8_FETCH_RES
         trace_stamp(p.trace, vb, 2);
         if (!has_next) break;
-#pragma unroll
-        for (int i = 0; i < MB; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+        kloop::zero(acc);
         vb = vbn; m0 = m0n; n0 = n0n; uA = uAn; uB = uBn;
         trace_stamp(p.trace, vb, 0);
     }
 #undef PV_V8_EVEN
 #undef PV_V8_ODD
-#undef PV_V8_FSTEP
-#undef PV_V8_PAIR
     __builtin_amdgcn_s_waitcnt(0x0F70);     // the dead prefetches behind the last tile must land before the LDS is handed on
 }
 
@@ -1482,11 +1176,7 @@ template <typename T, int MB>
 int launch_v7(const GemmParams& p, hipStream_t stream) {
     const int ntm = (p.M + 64 * MB - 1) / (64 * MB), ntn = (p.N + 255) / 256;
     {
-        constexpr double EBd = DT<T>::kBytes;
-        const double mn = (double)p.M * p.N;
-        double outs = 1.0;
-        if (p.epi == PV_EPI_RESID) outs = 2.0 + (p.out0 ? 1.0 : 0.0);
-        if (p.epi == PV_EPI_ACT) outs = 1.0 + (p.out0 ? 1.0 : 0.0);
+        const GemmCost cost = gemm_cost<T>(p);
         const dim3 grid(ntm * ntn), block(512);
         // the software-pipelined K loop covers plain A operands and whole 64-byte slabs
         // K loop: 2 = full-line form (whole 128-byte slabs: every B/32, L/14 shape), 1 = pipelined 64-byte slabs, 0 = the
@@ -1505,8 +1195,8 @@ int launch_v7(const GemmParams& p, hipStream_t stream) {
         const int stagger = g_pv_tuning.gemm_stagger;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         const bool timed = !g_pv_tuning.prof_markers &&
-                           pv_prof_events(PV_PROF_GEMM, 2.0 * mn * p.K, ((double)p.M * p.K + (double)p.N * p.K + outs * mn) * EBd, &ev0, &ev1);
-        ProfScope prof(timed ? PV_PROF__COUNT : PV_PROF_GEMM, stream, 2.0 * mn * p.K, ((double)p.M * p.K + (double)p.N * p.K + outs * mn) * EBd);
+                           pv_prof_events(PV_PROF_GEMM, cost.flops, cost.bytes, &ev0, &ev1);
+        ProfScope prof(timed ? PV_PROF__COUNT : PV_PROF_GEMM, stream, cost.flops, cost.bytes);
 #define PV_V8_LAUNCH(EPI, ACT)                                                                                                   \
     do {                                                                                                                         \
         if (timed) hipExtLaunchKernelGGL((gemm_kernel_v8<T, MB, EPI, ACT>), pgrid, block, 0, stream, ev0, ev1, 0, p, ntiles, stagger); \

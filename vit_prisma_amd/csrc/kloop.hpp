@@ -1,0 +1,392 @@
+// The main loop of the one-workgroup-per-CU MFMA kernels (gfx950): gemm_kernel_v7 / gemm_kernel_v8 (gemm.hip, bf16) and
+// sae_enc_gemm_kernel (sae_enc.hip, fp16).  One 512-thread workgroup (8 waves as 2 (M) x 4 (N)) multiplies a (64*MB) x 256 tile;
+// a wave owns (32*MB) x 64 outputs = MB x 2 accumulators of v_mfma_f32_32x32x16.  The operands are DMA'd straight into LDS
+// (buffer_load ... lds) in PIECES of 1 KiB = one wave-instruction; wave w moves pieces w, w + 8, ... of a slab's A part and of its
+// B part.  What is here, once:
+//   * the tile order (virtual block id -> tile), TileOrder
+//   * the geometry of a ring slot -- which LDS address a piece lands at, which source column a lane fetches, where a lane reads
+//     its MFMA fragments -- for 64-byte K slabs (Ring64) and for 128-byte ones (Ring128)
+//   * the three K-loop forms with their drivers (prologue issues, ring-unrolled loop, tails):
+//       KLOOP_RUN_FETCH_AFTER_BARRIER 64-byte slabs, four slots; any A operand, K tails             (LP = 0)
+//       KLOOP_RUN_PIPELINED64         64-byte slabs, four slots, software-pipelined                 (LP = 1)
+//       KLOOP_RUN_FULL_LINE           128-byte slabs (whole cache lines), two slots                 (LP = 2)
+//     and step_full_line on its own for the persistent kernel, whose driver walks tiles.
+// What a user supplies: the MFMA operand type (Bf16 / F16), MB, its __shared__ slot objects, its two buffer descriptors and a
+// SOURCE FUNCTOR  src(kt, j) -> byte offset into the A (j < pieces of A) or B descriptor of the piece j this wave moves for slab kt,
+// or DEAD (LP = 0: a functor per slab, see there).  That functor is where the users differ: plain rows, the patch gather, a K
+// tail, an explicit N bound, a slab index that runs into the next tile.
+//
+// Three rules every line below keeps (each was paid for with a drained DMA queue):
+//   * SELECTS, NOT BRANCHES, around an LDS-DMA: hipcc's waitcnt pass answers a conditionally executed LDS-DMA with
+//     s_waitcnt vmcnt(0) before the next ds_read.  A piece that must not load gets the offset DEAD (past every descriptor's range:
+//     the DMA zero-fills); source functors use bitwise |, & so that their conditions compile to selects.
+//   * ONE __shared__ OBJECT PER SLOT, declared by the kernel and handed in as pointers: hipcc's alias scopes are per LDS variable.
+//     Only then can it prove that the ds_reads of one slot do not alias the DMA writes in flight to the others; with a single
+//     array it waits vmcnt(0) before the first ds_read of every step.  (These functions are force-inlined into the kernel, so the
+//     pointers are the objects again by the time that pass runs.)
+//   * THE ISSUE ORDER IS THE SCHEDULE in the pipelined forms: MFMA pair | DMA piece + fragment refill | MFMA pair | ..., pinned with
+//     sched_barrier.  Left to itself hipcc sinks the refills to the end of the (half-)slab and waits for them right behind the
+//     barrier, with the matrix pipe idle.
+// The waits are COUNTED s_waitcnt vmcnt(n) across a raw s_barrier (simm16 0x0F70 | n: expcnt 7, lgkmcnt 15 -- only vmcnt is waited
+// on): __syncthreads() would drain the queue.  Every wave retires the same number of pieces per slab, so n is a compile-time figure.
+#pragma once
+#include "pv_common.hpp"
+
+namespace kloop {
+
+typedef __attribute__((address_space(3))) void* lds_ptr_t;      // destination of an LDS-DMA
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+constexpr unsigned DEAD = 0xffffff00u;                          // source offset of a piece that must not load
+
+// operand-type tags
+struct Bf16 {};
+struct F16 {};
+__device__ __forceinline__ f32x16 mfma(Bf16, const uint4& a, const uint4& b, const f32x16& c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma(F16, const uint4& a, const uint4& b, const f32x16& c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+// one A fragment against the wave's two B fragments
+template <class OP>
+__device__ __forceinline__ void mfma_pair(f32x16 (&acc)[2], const uint4& a, const uint4 (&b)[2]) {
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) acc[ni] = mfma(OP{}, a, b[ni], acc[ni]);
+}
+
+__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t& rs, unsigned char* dst, unsigned off) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)dst, 16, off, 0, 0, 0);
+}
+__device__ __forceinline__ void pin() { __builtin_amdgcn_sched_barrier(0); }
+
+// ---------------------------------------------------------------------------------------------------
+// Tile order.  Block b of a launch runs on XCD b % 8: xcd_run() is the bijection that gives each XCD a contiguous run of the
+// linear order, so that neighbours in that order share an L2.  (A persistent kernel passes its virtual block id and the tile
+// count: vb and vb + k * grid sit on the same XCD.)
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int xcd_run(int bid, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+// The linear order itself: column blocks of <= 8 N-tiles, M-major inside a block.  The B panel of a block (8 x TN rows x K) stays
+// resident in the XCD's 4 MB L2 while the M range streams past once per block, instead of the whole weight matrix being
+// re-streamed every few M-tiles (PMC: L2-miss reads were 4x the algorithmic bytes with plain N-fastest order).
+template <int TM, int TN>
+struct TileOrder {
+    int ntn, ntm, wblk;
+    __device__ __forceinline__ TileOrder(int M, int N) {
+        ntn = (N + TN - 1) / TN;
+        ntm = (M + TM - 1) / TM;
+        const int nblk = (ntn + 7) / 8;
+        wblk = (ntn + nblk - 1) / nblk;
+    }
+    // position swz in the order -> tile
+    __device__ __forceinline__ void at(int swz, int& tile_m, int& tile_n) const {
+        const int blk = swz / (ntm * wblk);
+        const int rem = swz - blk * (ntm * wblk);
+        const int wcur = min(wblk, ntn - blk * wblk);
+        tile_m = rem / wcur;
+        tile_n = blk * wblk + (rem - tile_m * wcur);
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------
+// Slot of 64-byte K slabs: (64*MB + 256) rows x 64 B, the A rows first.  A row is 4 chunks of 16 B and 4 rows share a 256-byte
+// bank row; chunk c of row r sits at position c ^ swz64(r), applied on the DMA source column and on the fragment reads
+// (conflict-free ds_read_b128).  A piece is 16 rows; per slab a wave issues NA = ceil(4*MB / 8) A pieces + 2 B pieces.  At MB = 5
+// waves 4..7 have only 2 real A pieces -- their third is a DEAD DMA into a pad, so that every wave retires the same number.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int swz64(int row) { return (row >> 2) & 3; }
+
+template <int MB>
+struct Ring64 {
+    static constexpr int A_BYTES = 64 * MB * 64, B_BYTES = 256 * 64, SLOT = A_BYTES + B_BYTES;
+    static constexpr int NA = (4 * MB + 7) / 8;
+    static constexpr bool PAD = (4 * MB) % 8 != 0;
+    static constexpr int PAD_BYTES = PAD ? 8192 : 16;
+    static constexpr int NPIECE = NA + 2;                 // pieces per wave per slab
+    static constexpr int PIECE_STRIDE = 128;              // rows between a wave's consecutive pieces
+    static_assert(4 * SLOT + PAD_BYTES <= 160 * 1024, "one workgroup per CU");
+    static_assert(3 * NPIECE <= 15, "the vmcnt immediates use the low 4 bits only");
+    int wave;
+    unsigned char* pad;
+    int a_row, b_row, co0, co1;
+    __device__ __forceinline__ Ring64(int lane, int wave_, unsigned char* pad_) : wave(wave_), pad(pad_) {
+        const int l31 = lane & 31, half = lane >> 5, sw = swz64(l31);
+        co0 = ((0 + half) ^ sw) * 16;
+        co1 = ((2 + half) ^ sw) * 16;
+        a_row = ((wave >> 2) * 32 * MB + l31) * 64;
+        b_row = A_BYTES + ((wave & 3) * 64 + l31) * 64;
+    }
+    // the row (of the slab's A or B part) and the source byte column that this lane fetches for this wave's piece j
+    __device__ __forceinline__ int piece_row(int lane, int j) const { return (j * 8 + wave) * 16 + (lane >> 2); }
+    __device__ static __forceinline__ int piece_col(int lane, int row) { return ((lane & 3) ^ swz64(row)) * 16; }
+    __device__ __forceinline__ bool real_a(int j) const { return j * 8 + wave < 4 * MB; }      // (uniform)
+    // piece j of a slab (j < NA: of A, else of B) from source offset `off` into `slot`
+    __device__ __forceinline__ void issue(const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB, unsigned char* slot,
+                                          int j, unsigned off) const {
+        if (j < NA) {
+            unsigned char* dst = slot + (j * 8 + wave) * 1024;
+            if constexpr (PAD) { if (j == NA - 1) dst = real_a(j) ? dst : pad + wave * 1024; }
+            dma16(rsA, dst, off);
+        } else {
+            dma16(rsB, slot + A_BYTES + ((j - NA) * 8 + wave) * 1024, off);
+        }
+    }
+    // fragments of half-slab h (32 bytes of K): block mi of A, block ni of B
+    __device__ __forceinline__ uint4 rd_a(const unsigned char* slot, int h, int mi) const {
+        return *reinterpret_cast<const uint4*>(slot + a_row + mi * 2048 + (h == 0 ? co0 : co1));
+    }
+    __device__ __forceinline__ uint4 rd_b(const unsigned char* slot, int h, int ni) const {
+        return *reinterpret_cast<const uint4*>(slot + b_row + ni * 2048 + (h == 0 ? co0 : co1));
+    }
+};
+
+// all pieces of slab kt into `slot` (source functor)
+template <int MB, class Src>
+__device__ __forceinline__ void issue_slab64(const Ring64<MB>& g, const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB,
+                                             int kt, unsigned char* slot, const Src& src) {
+#pragma unroll
+    for (int j = 0; j < Ring64<MB>::NPIECE; ++j) g.issue(rsA, rsB, slot, j, src(kt, j));
+}
+
+// LP = 0, barrier-then-fetch.  Slab kt+3 is issued (into nxt3, the slot multiplied in step kt-1) while slab kt (in cur) is
+// multiplied; at step kt slab kt must have landed, the 2 * NPIECE pieces of slabs kt+1, kt+2 stay in flight across the barrier.
+// This form takes the patch gather and K tails, whose sources have terms per slab: its functor is  issue(kt, slot), which puts
+// all NPIECE pieces of slab kt into the slot through g.issue().
+template <class OP, int MB, class Issue>
+__device__ __forceinline__ void step_fetch_after_barrier(f32x16 (&acc)[MB][2], const Ring64<MB>& g, int kt, unsigned char* cur,
+                                                         unsigned char* nxt3, const Issue& issue) {
+    __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * Ring64<MB>::NPIECE));
+    __builtin_amdgcn_s_barrier();
+    issue(kt + 3, nxt3);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        uint4 a[MB], b[2];
+#pragma unroll
+        for (int mi = 0; mi < MB; ++mi) a[mi] = g.rd_a(cur, h, mi);
+        b[0] = g.rd_b(cur, h, 0);
+        b[1] = g.rd_b(cur, h, 1);
+#pragma unroll
+        for (int mi = 0; mi < MB; ++mi) mfma_pair<OP>(acc[mi], a[mi], b);
+    }
+}
+
+// LP = 1, software-pipelined.  The loop above has every wave arrive at the slab's barrier with empty fragment registers: both
+// waves of a SIMD then issue their DMA pieces and their first ds_reads and sit out the LDS latency with the matrix pipe idle.
+// Here the fragments of a half-slab are fetched while the previous half-slab is multiplied (each A fragment is refilled right
+// behind the two MFMAs that consumed it), the barrier of slab s+1 sits in the MIDDLE of step s (between its two halves: by then
+// every read of slab s has been issued, and the second half's operands are already in registers), and the DMA pieces of slab s+4
+// go out one per MFMA pair during the second half, into the slot the barrier has just freed.  Ring depth as before: at the barrier
+// of slab s+1 the pieces of slabs s+2 and s+3 stay in flight.  Whole 64-byte slabs only.
+//   step kt: slab kt in cur (visible), slab kt+1 in nxt; fa / fb0 hold the first half of slab kt
+template <class OP, int MB, class Src>
+__device__ __forceinline__ void step_pipelined64(f32x16 (&acc)[MB][2], uint4 (&fa)[MB], uint4 (&fb0)[2], uint4 (&fb1)[2],
+                                                 const Ring64<MB>& g, const __amdgpu_buffer_rsrc_t& rsA,
+                                                 const __amdgpu_buffer_rsrc_t& rsB, int kt, unsigned char* cur, unsigned char* nxt,
+                                                 const Src& src) {
+    constexpr int NPIECE = Ring64<MB>::NPIECE;
+    static_assert(NPIECE <= MB && MB >= 2, "one DMA piece per MFMA pair; the B refill rides behind pair 1");
+#pragma unroll
+    for (int mi = 0; mi < MB; ++mi) {
+        mfma_pair<OP>(acc[mi], fa[mi], fb0);
+        pin();
+        fa[mi] = g.rd_a(cur, 1, mi);
+        if (mi == 1) { fb1[0] = g.rd_b(cur, 1, 0); fb1[1] = g.rd_b(cur, 1, 1); }
+        pin();
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * NPIECE));
+    __builtin_amdgcn_s_barrier();
+    pin();
+#pragma unroll
+    for (int mi = 0; mi < MB; ++mi) {
+        mfma_pair<OP>(acc[mi], fa[mi], fb1);
+        pin();
+        fa[mi] = g.rd_a(nxt, 0, mi);
+        if (mi == 1) { fb0[0] = g.rd_b(nxt, 0, 0); fb0[1] = g.rd_b(nxt, 0, 1); }
+        if (mi < NPIECE) g.issue(rsA, rsB, cur, mi, src(kt + 4, mi));
+        pin();
+    }
+}
+// its prologue: four slabs issued, slab 0 landed, the first half of slab 0 in the fragment registers
+template <int MB, class Src>
+__device__ __forceinline__ void prologue_pipelined64(uint4 (&fa)[MB], uint4 (&fb0)[2], const Ring64<MB>& g,
+                                                     const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB,
+                                                     unsigned char* r0, unsigned char* r1, unsigned char* r2, unsigned char* r3,
+                                                     const Src& src) {
+    issue_slab64(g, rsA, rsB, 0, r0, src);
+    issue_slab64(g, rsA, rsB, 1, r1, src);
+    issue_slab64(g, rsA, rsB, 2, r2, src);
+    issue_slab64(g, rsA, rsB, 3, r3, src);
+    __builtin_amdgcn_s_waitcnt(0x0F70 | (3 * Ring64<MB>::NPIECE));
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int mi = 0; mi < MB; ++mi) fa[mi] = g.rd_a(r0, 0, mi);
+    fb0[0] = g.rd_b(r0, 0, 0);
+    fb0[1] = g.rd_b(r0, 0, 1);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Slot of 128-byte K slabs: whole cache lines -- a piece is 8 rows x 128 B = 8 lines instead of 16 half lines (64-byte slabs pull
+// every operand line through the L1 twice, 1 us apart, and the texture addresser is busy 55-79 % of the launch:
+// profiles/r02_notes.md).  A row is 8 chunks; chunk c of row r at position c ^ swz128(r): the 16 rows of a ds_read_b128 lane group
+// (8 even, 8 odd) then cover all 64 banks.  Per slab a wave issues MB A pieces + 4 B pieces.
+// SPLIT: the A and the B part of a slot are separate __shared__ objects (the persistent kernel); else the B part follows the A
+// part in one object and both slot pointers of a call are that object.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int swz128(int row) { return (row >> 1) & 7; }
+
+template <int MB, bool SPLIT = false>
+struct Ring128 {
+    static constexpr int A_BYTES = 64 * MB * 128, B_BYTES = 256 * 128, SLOT = A_BYTES + B_BYTES;
+    static constexpr int B_BASE = SPLIT ? 0 : A_BYTES;
+    static constexpr int NPIECE = MB + 4;                 // pieces per wave per slab
+    static constexpr int PIECE_STRIDE = 64;               // rows between a wave's consecutive pieces
+    static_assert(MB >= 2, "the B refill rides behind MFMA pair 1");
+    int wave;
+    int a_row, b_row, fco[4];
+    __device__ __forceinline__ Ring128(int lane, int wave_) : wave(wave_) {
+        const int l31 = lane & 31, half = lane >> 5, fsw = swz128(l31);
+        a_row = ((wave >> 2) * 32 * MB + l31) * 128;
+        b_row = B_BASE + ((wave & 3) * 64 + l31) * 128;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) fco[h] = ((2 * h + half) ^ fsw) * 16;
+    }
+    // the row (of the slab's A or B part) and the source byte column that this lane fetches for this wave's piece 0
+    __device__ __forceinline__ int piece_row(int lane) const { return wave * 8 + (lane >> 3); }
+    __device__ __forceinline__ unsigned piece_col(int lane) const { return (unsigned)(((lane & 7) ^ swz128(piece_row(lane))) * 16); }
+    // piece j of a slab (j < MB: of A, else of B) from source offset `off` into the slot
+    __device__ __forceinline__ void issue(const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB, unsigned char* slotA,
+                                          unsigned char* slotB, int j, unsigned off) const {
+        if (j < MB) dma16(rsA, slotA + (j * 8 + wave) * 1024, off);
+        else dma16(rsB, slotB + B_BASE + ((j - MB) * 8 + wave) * 1024, off);
+    }
+    // fragments of k-step h (16 elements of K): block mi of A, block ni of B
+    __device__ __forceinline__ uint4 rd_a(const unsigned char* slotA, int h, int mi) const {
+        return *reinterpret_cast<const uint4*>(slotA + a_row + mi * 4096 + fco[h]);
+    }
+    __device__ __forceinline__ uint4 rd_b(const unsigned char* slotB, int h, int ni) const {
+        return *reinterpret_cast<const uint4*>(slotB + b_row + ni * 4096 + fco[h]);
+    }
+    // k-step 0 of a slab into the fragment registers a step starts from
+    __device__ __forceinline__ void first_fragments(uint4 (&fa)[MB], uint4 (&fb)[2][2], const unsigned char* slotA,
+                                                    const unsigned char* slotB) const {
+#pragma unroll
+        for (int mi = 0; mi < MB; ++mi) fa[mi] = rd_a(slotA, 0, mi);
+        fb[0][0] = rd_b(slotB, 0, 0);
+        fb[0][1] = rd_b(slotB, 0, 1);
+    }
+    // head of a slab stream: slab 0 entirely, then the A pieces of slab 1 (its B pieces ride on step 0's first k-step)
+    template <class Src>
+    __device__ __forceinline__ void prologue(const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB, unsigned char* a0,
+                                             unsigned char* b0, unsigned char* a1, unsigned char* b1, const Src& src) const {
+#pragma unroll
+        for (int j = 0; j < NPIECE; ++j) issue(rsA, rsB, a0, b0, j, src(0, j));
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int j = 0; j < MB; ++j) issue(rsA, rsB, a1, b1, j, src(1, j));
+    }
+};
+
+// LP = 2, full-line step: the software pipeline of run_pipelined64 on four 16-element k-steps per slab.  Slab kt in cur (visible),
+// slab kt+1 arriving in nxt; fa / fb[0] hold k-step 0 of slab kt.  The barrier of slab kt+1 sits before the LAST k-step of slab kt
+// (every read of slab kt has been issued by then); the A pieces of slab kt+2 go out behind the MFMA pairs of that last k-step
+// (into the slot the barrier freed), the B pieces of slab kt+1 behind those of the first k-step.  One slab of prefetch distance
+// (the slot it lands in is read until the barrier), so the wait before the barrier is vmcnt(0).
+template <class OP, int MB, bool SPLIT, class Src>
+__device__ __forceinline__ void step_full_line(f32x16 (&acc)[MB][2], uint4 (&fa)[MB], uint4 (&fb)[2][2], const Ring128<MB, SPLIT>& g,
+                                               const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB, int kt,
+                                               unsigned char* curA, unsigned char* curB, unsigned char* nxtA, unsigned char* nxtB,
+                                               const Src& src) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        if (h == 3) {
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            __builtin_amdgcn_s_barrier();
+            pin();
+        }
+#pragma unroll
+        for (int mi = 0; mi < MB; ++mi) {
+            mfma_pair<OP>(acc[mi], fa[mi], fb[h & 1]);
+            pin();
+            // (fco[] indices kept in range: an out-of-bounds index in a dead arm defeats SROA)
+            fa[mi] = h < 3 ? g.rd_a(curA, h < 3 ? h + 1 : 0, mi) : g.rd_a(nxtA, 0, mi);
+            if (mi == 1) {
+                fb[(h + 1) & 1][0] = h < 3 ? g.rd_b(curB, h < 3 ? h + 1 : 0, 0) : g.rd_b(nxtB, 0, 0);
+                fb[(h + 1) & 1][1] = h < 3 ? g.rd_b(curB, h < 3 ? h + 1 : 0, 1) : g.rd_b(nxtB, 0, 1);
+            }
+            if (h == 3) g.issue(rsA, rsB, curA, curB, mi, src(kt + 2, mi));
+            if (h == 0) {
+#pragma unroll
+                for (int jb = mi; jb < 4; jb += MB) g.issue(rsA, rsB, nxtA, nxtB, MB + jb, src(kt + 1, MB + jb));
+            }
+            pin();
+        }
+    }
+}
+
+template <int MB>
+__device__ __forceinline__ void zero(f32x16 (&acc)[MB][2]) {
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+}
+
+}  // namespace kloop
+
+// ---------------------------------------------------------------------------------------------------
+// The drivers: prologue issues, the ring-unrolled loop, the tails.  MACROS, expanded in the kernel's own scope, around the step
+// templates above: written as one more level of function template, hipcc no longer folds the liveness test of a piece that the
+// loop's own bound decides (slab kt+1 is always live inside the full-line loop) -- a select and a register per piece, 4 to 10
+// VGPRs on kernels that sit at 235 - 256.  OP: kloop::Bf16 / kloop::F16; G: the Ring64 / Ring128 object; R0..: the slot objects;
+// NK: slabs of K (64-byte ones, rounded up, for the first two; whole 128-byte ones for the third); ISSUE / SRC: the functor.
+// ---------------------------------------------------------------------------------------------------
+#define KLOOP_RUN_FETCH_AFTER_BARRIER(OP, ACC, G, R0, R1, R2, R3, NK, ISSUE)                                 \
+    do {                                                                                                   \
+        ISSUE(0, R0);                                                                                      \
+        ISSUE(1, R1);                                                                                      \
+        ISSUE(2, R2);                                                                                      \
+        int kl_kt = 0;                                                                                     \
+        for (; kl_kt + 4 <= (NK); kl_kt += 4) {                                                            \
+            kloop::step_fetch_after_barrier<OP>(ACC, G, kl_kt, R0, R3, ISSUE);                             \
+            kloop::step_fetch_after_barrier<OP>(ACC, G, kl_kt + 1, R1, R0, ISSUE);                         \
+            kloop::step_fetch_after_barrier<OP>(ACC, G, kl_kt + 2, R2, R1, ISSUE);                         \
+            kloop::step_fetch_after_barrier<OP>(ACC, G, kl_kt + 3, R3, R2, ISSUE);                         \
+        }                                                                                                  \
+        if (kl_kt < (NK)) kloop::step_fetch_after_barrier<OP>(ACC, G, kl_kt, R0, R3, ISSUE);               \
+        if (kl_kt + 1 < (NK)) kloop::step_fetch_after_barrier<OP>(ACC, G, kl_kt + 1, R1, R0, ISSUE);       \
+        if (kl_kt + 2 < (NK)) kloop::step_fetch_after_barrier<OP>(ACC, G, kl_kt + 2, R2, R1, ISSUE);       \
+    } while (0)
+
+#define KLOOP_RUN_PIPELINED64(OP, MB, ACC, G, RSA, RSB, R0, R1, R2, R3, NK, SRC)                           \
+    do {                                                                                                   \
+        uint4 kl_fa[MB], kl_fb0[2], kl_fb1[2];                                                             \
+        kloop::prologue_pipelined64(kl_fa, kl_fb0, G, RSA, RSB, R0, R1, R2, R3, SRC);                      \
+        int kl_kt = 0;                                                                                     \
+        for (; kl_kt + 4 <= (NK); kl_kt += 4) {                                                            \
+            kloop::step_pipelined64<OP>(ACC, kl_fa, kl_fb0, kl_fb1, G, RSA, RSB, kl_kt, R0, R1, SRC);      \
+            kloop::step_pipelined64<OP>(ACC, kl_fa, kl_fb0, kl_fb1, G, RSA, RSB, kl_kt + 1, R1, R2, SRC);  \
+            kloop::step_pipelined64<OP>(ACC, kl_fa, kl_fb0, kl_fb1, G, RSA, RSB, kl_kt + 2, R2, R3, SRC);  \
+            kloop::step_pipelined64<OP>(ACC, kl_fa, kl_fb0, kl_fb1, G, RSA, RSB, kl_kt + 3, R3, R0, SRC);  \
+        }                                                                                                  \
+        if (kl_kt < (NK)) kloop::step_pipelined64<OP>(ACC, kl_fa, kl_fb0, kl_fb1, G, RSA, RSB, kl_kt, R0, R1, SRC);         \
+        if (kl_kt + 1 < (NK)) kloop::step_pipelined64<OP>(ACC, kl_fa, kl_fb0, kl_fb1, G, RSA, RSB, kl_kt + 1, R1, R2, SRC); \
+        if (kl_kt + 2 < (NK)) kloop::step_pipelined64<OP>(ACC, kl_fa, kl_fb0, kl_fb1, G, RSA, RSB, kl_kt + 2, R2, R3, SRC); \
+    } while (0)
+
+#define KLOOP_RUN_FULL_LINE(OP, MB, ACC, G, RSA, RSB, R0, R1, NK2, SRC)                                    \
+    do {                                                                                                   \
+        uint4 kl_fa[MB], kl_fb[2][2];                                                                      \
+        (G).prologue(RSA, RSB, R0, R0, R1, R1, SRC);                                                       \
+        (G).first_fragments(kl_fa, kl_fb, R0, R0);                                                         \
+        int kl_kt = 0;                                                                                     \
+        for (; kl_kt + 2 <= (NK2); kl_kt += 2) {                                                           \
+            kloop::step_full_line<OP>(ACC, kl_fa, kl_fb, G, RSA, RSB, kl_kt, R0, R0, R1, R1, SRC);         \
+            kloop::step_full_line<OP>(ACC, kl_fa, kl_fb, G, RSA, RSB, kl_kt + 1, R1, R1, R0, R0, SRC);     \
+        }                                                                                                  \
+        if (kl_kt < (NK2)) kloop::step_full_line<OP>(ACC, kl_fa, kl_fb, G, RSA, RSB, kl_kt, R0, R0, R1, R1, SRC); \
+    } while (0)

@@ -26,6 +26,7 @@
 // row-contiguous k-slices ([K][rows]: four 4-byte LDS reads, lanes on consecutive rows).  f^T, dH^T, dY and sae_in of G4 / G5
 // are therefore the buffers as they lie, read "the other way".
 #include <algorithm>
+#include "kloop.hpp"
 #include "sae.hpp"
 #include <cstring>
 
@@ -154,9 +155,7 @@ __global__ __launch_bounds__(256, 2) void dense_gemm_kernel(const DenseGemm p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     // XCD-aware bijective remap (block b runs on XCD b % 8): each XCD gets a contiguous run of tiles, N fastest
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int swz = kloop::xcd_run(blockIdx.x, gridDim.x);
     const int ntn = (p.N + DG_BN - 1) / DG_BN;
     // Tile order inside an XCD's run.  N fastest (group 0) lets the 64 tiles an XCD runs at a time share ONE row slab and stream 64
     // different column slabs: at a wide output (the encoder and dH GEMMs: 192 column tiles of 393 KB operand rows each) every XCD
@@ -272,7 +271,7 @@ __global__ __launch_bounds__(256, 2) void dense_gemm_kernel(const DenseGemm p) {
             store_slab(0);
         }
         __syncthreads();
-        const int sw = (l31 >> 2) & 3;
+        const int sw = kloop::swz64(l31);
         for (int kt = 0; kt < nk; ++kt) {
             const int buf = kt & 1;
 #ifndef PV_DG_NOLOAD                                   // (timing ablations of tools/build_variant.sh builds: results are wrong with any of them)

@@ -30,12 +30,10 @@
 // row falls back): slow, never wrong.
 #include <atomic>
 
+#include "kloop.hpp"
 #include "sae.hpp"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct EncParams {
     const void* A;            // [M][lda] fp16
@@ -64,8 +62,8 @@ __device__ __forceinline__ float ord2f(uint32_t o) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// filter GEMM: the v7 mainloop of gemm.hip (one 8-wave workgroup per CU, 256 x 256 tile, 64-byte K slabs DMA'd into a
-// 4-slot LDS ring three slabs ahead, counted vmcnt across a raw s_barrier) on fp16 operands, with an epilogue that
+// filter GEMM: the main loop of gemm_kernel_v7 (kloop.hpp: one 8-wave workgroup per CU, 256 x 256 tile, K slabs DMA'd into an
+// LDS ring, counted vmcnt across a raw s_barrier; LP selects the loop form as there) on fp16 operands, with an epilogue that
 // stores nothing but the hits.  MODE 0: plain fp32 store of acc + bias (the sample of pass 0).
 // ---------------------------------------------------------------------------------------------------
 // MB_: 32-row blocks per wave along M -- 4 (256 x 256 tiles) everywhere but the sample pass at the bench shape, whose 4096 x 1536 output
@@ -74,8 +72,11 @@ template <int MODE, int LP = 0, bool ONE = false, int MB_ = 4>
 __global__ __launch_bounds__(512, 2) void sae_enc_gemm_kernel(const EncParams p) {
     constexpr int MB = MB_, TM = 64 * MB, TN = 256;
     static_assert(MB == 4 || (MB == 2 && LP == 2 && MODE == 0), "the 128-row tile exists in the full-line form of the sample pass only");
-    constexpr int A_BYTES = TM * 64, B_BYTES = TN * 64, SLOT = A_BYTES + B_BYTES;
-    // LP == 2 (full-line K slabs): two slots of 128-byte rows in ring0 / ring1, ring2 / ring3 shrink to stubs
+    using R64 = kloop::Ring64<MB>;
+    using R128 = kloop::Ring128<MB>;
+    constexpr int SLOT = 64 * (TM + TN);
+    // the ring slots, one object each (kloop.hpp).  LP == 2 (full-line K slabs): two slots of 128-byte rows in ring0 / ring1,
+    // ring2 / ring3 shrink to stubs
     __shared__ __attribute__((aligned(16))) unsigned char ring0[LP == 2 ? 2 * SLOT : SLOT];
     __shared__ __attribute__((aligned(16))) unsigned char ring1[LP == 2 ? 2 * SLOT : SLOT];
     __shared__ __attribute__((aligned(16))) unsigned char ring2[LP == 2 ? 16 : SLOT];
@@ -87,19 +88,13 @@ __global__ __launch_bounds__(512, 2) void sae_enc_gemm_kernel(const EncParams p)
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    // tile order as in gemm_kernel_v7: column blocks of <= 8 N-tiles, M-major inside (a block's weight panel -- 8 x 256 rows
-    // x K fp16 = 3 MB at K = 768 -- stays in the XCD's L2 while the token rows stream past)
-    const int ntn = (p.N + TN - 1) / TN, ntm = (p.M + TM - 1) / TM;
-    const int nblk = (ntn + 7) / 8;
-    const int wblk = (ntn + nblk - 1) / nblk;
-    const int blk = swz / (ntm * wblk);
-    const int rem = swz - blk * (ntm * wblk);
-    const int wcur = min(wblk, ntn - blk * wblk);
-    const int tile_m = rem / wcur, tile_n = blk * wblk + (rem - tile_m * wcur);
+    // tile order as in gemm_kernel_v7 (a column block's weight panel -- 8 x 256 rows x K fp16 = 3 MB at K = 768 -- stays in the
+    // XCD's L2 while the token rows stream past)
+    const int swz = kloop::xcd_run(blockIdx.x, gridDim.x);
+    const kloop::TileOrder<TM, TN> order(p.M, p.N);
+    const int ntn = order.ntn;
+    int tile_m, tile_n;
+    order.at(swz, tile_m, tile_n);
     const int m0 = tile_m * TM, n0 = tile_n * TN;
 
     if constexpr (MODE == 1) {
@@ -125,69 +120,14 @@ __global__ __launch_bounds__(512, 2) void sae_enc_gemm_kernel(const EncParams p)
 #endif
     ENC_STAMP(0);
     const unsigned Kb = (unsigned)p.K * 2u;
-    const int nk = (int)((Kb + 63) / 64);
-    const bool ktail = (Kb % 64) != 0;
+    const unsigned ldaB = (unsigned)p.lda * 2u;
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void*>(p.A), 0, (int)((unsigned)p.M * (unsigned)p.lda * 2u), 0x00020000);
+        const_cast<void*>(p.A), 0, (int)((unsigned)p.M * ldaB), 0x00020000);                        // rows >= M land past the range: zero fill
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.B), 0, (int)p.b_span, 0x00020000);
 
-    unsigned offA[2], kcA[2], offB[2], kcB[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int row = (j * 8 + wave) * 16 + (lane >> 2);
-        const int kc = (lane & 3) ^ ((row >> 2) & 3);
-        kcA[j] = kcB[j] = kc * 16;
-        offA[j] = (unsigned)(m0 + row) * (unsigned)p.lda * 2u + kc * 16;       // rows >= M land past the descriptor: zero fill
-        offB[j] = (n0 + row < p.N) ? (unsigned)(n0 + row) * p.ldb_bytes + kc * 16 : 0xffffff00u;
-    }
-    auto issue = [&](int kt, unsigned char* slot) {
-        const unsigned kbase = (unsigned)kt * 64;
-        const bool dead = kt >= nk;
-        // (selects only: a branch around an LDS-DMA makes hipcc drain the queue before the next ds_read)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            unsigned o = offA[j] + kbase;
-            o = (dead | (ktail & (kbase + kcA[j] >= Kb))) ? 0xffffff00u : o;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)(slot + (j * 8 + wave) * 1024), 16, o, 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            unsigned o = offB[j] + kbase;
-            o = (dead | (offB[j] == 0xffffff00u) | (ktail & (kbase + kcB[j] >= Kb))) ? 0xffffff00u : o;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(slot + A_BYTES + (j * 8 + wave) * 1024), 16, o, 0, 0, 0);
-        }
-    };
-
     f32x16 acc[MB][2];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-
+    kloop::zero(acc);
     const int l31 = lane & 31, half = lane >> 5;
-    const int sw = (l31 >> 2) & 3;
-    const int co0 = ((0 + half) ^ sw) * 16, co1 = ((2 + half) ^ sw) * 16;
-    const int a_row = (wm * 32 * MB + l31) * 64;
-    const int b_row = A_BYTES + (wn * 64 + l31) * 64;
-    auto compute = [&](const unsigned char* slot) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int co = j == 0 ? co0 : co1;
-            uint4 a[MB], b[2];
-#pragma unroll
-            for (int mi = 0; mi < MB; ++mi) a[mi] = *reinterpret_cast<const uint4*>(slot + a_row + mi * 2048 + co);
-            b[0] = *reinterpret_cast<const uint4*>(slot + b_row + co);
-            b[1] = *reinterpret_cast<const uint4*>(slot + b_row + 2048 + co);
-#pragma unroll
-            for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                        __builtin_bit_cast(f16x8, a[mi]), __builtin_bit_cast(f16x8, b[ni]), acc[mi][ni], 0, 0, 0);
-        }
-    };
 
     // epilogue operands in flight before the K loop: this lane's two bias values and (MODE 1) the tile's 256 thresholds,
     // DMA'd into LDS (they are the oldest entries of the vmcnt queue, so the first counted wait retires them)
@@ -197,184 +137,65 @@ __global__ __launch_bounds__(512, 2) void sae_enc_gemm_kernel(const EncParams p)
     for (int ni = 0; ni < 2; ++ni) bias[ni] = (colb + ni * 32 < p.N) ? p.bias[(int64_t)(colb + ni * 32) * p.bias_stride] : 0.0f;
     if constexpr (MODE == 1) {
         const __amdgpu_buffer_rsrc_t rsT = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.thr), 0, p.M * 4, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsT, (lds_ptr_t)(trow + wave * 64), 4, (unsigned)(m0 + wave * 64 + lane) * 4u, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsT, (kloop::lds_ptr_t)(trow + wave * 64), 4, (unsigned)(m0 + wave * 64 + lane) * 4u, 0, 0, 0);
     }
 
-    if constexpr (LP == 0) {
-    // step kt: slab kt must have landed -- the 8 DMA instructions of slabs kt+1, kt+2 may stay in flight
-#define PV_ENC_STEP(KT, CUR, NXT3)                 \
-    __builtin_amdgcn_s_waitcnt(0x0F70 | 8);        \
-    __builtin_amdgcn_s_barrier();                  \
-    issue((KT) + 3, NXT3);                         \
-    compute(CUR);
-
-    issue(0, ring0);
-    issue(1, ring1);
-    issue(2, ring2);
-    int kt = 0;
-    for (; kt + 4 <= nk; kt += 4) {
-        PV_ENC_STEP(kt, ring0, ring3)
-        PV_ENC_STEP(kt + 1, ring1, ring0)
-        PV_ENC_STEP(kt + 2, ring2, ring1)
-        PV_ENC_STEP(kt + 3, ring3, ring2)
-    }
-    if (kt < nk) { PV_ENC_STEP(kt, ring0, ring3) }
-    if (kt + 1 < nk) { PV_ENC_STEP(kt + 1, ring1, ring0) }
-    if (kt + 2 < nk) { PV_ENC_STEP(kt + 2, ring2, ring1) }
-#undef PV_ENC_STEP
-    } else if constexpr (LP == 1) {
-        // software-pipelined form of the loop (gemm.hip, gemm_kernel_v7<..., LP = 1>): fragments of a half-slab refilled
-        // right behind the MFMA pair that consumed them, the slab's barrier between its two halves, the DMA pieces of
-        // slab s+4 one per MFMA pair in the second half.  Whole 64-byte slabs only (the launcher checks K % 32 == 0).
-        constexpr int NPIECE = 4;
-        const unsigned pA0 = (unsigned)(m0 + wave * 16 + (lane >> 2)) * (unsigned)p.lda * 2u + (((lane & 3) ^ ((lane >> 4) & 3)) * 16);
-        const unsigned strideA = 128u * (unsigned)p.lda * 2u;
-        auto issue_piece = [&](int kt, unsigned char* slot, int j) {
-            const unsigned kbase = (unsigned)kt * 64;
-            const bool dead = kt >= nk;
-            if (j < 2) {
-                const unsigned o = dead ? 0xffffff00u : pA0 + ((unsigned)j * strideA + kbase);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)(slot + (j * 8 + wave) * 1024), 16, o, 0, 0, 0);
-            } else {
-                const int jb = j - 2;
-                const unsigned o = (dead | (offB[jb] == 0xffffff00u)) ? 0xffffff00u : offB[jb] + kbase;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(slot + A_BYTES + (jb * 8 + wave) * 1024), 16, o, 0, 0, 0);
-            }
-        };
-        auto issue_all = [&](int kt, unsigned char* slot) {
+    // the K loop (kloop.hpp) on fp16 operands; the B rows (features) past N are made dead explicitly: the descriptor of a strided
+    // view of W_enc (the sample pass) does not end where N does
+    if constexpr (LP < 2) {
+        static_assert(LP == 2 || (R64::NA == 2 && !R64::PAD), "MB = 4: two A pieces and two B pieces per wave per slab");
+        const R64 g(lane, wave, nullptr);
+        const int nk = (int)((Kb + 63) / 64);
+        unsigned offA[2], offB[2], kc[2];
 #pragma unroll
-            for (int j = 0; j < NPIECE; ++j) issue_piece(kt, slot, j);
-        };
-        auto rdA = [&](const unsigned char* slot, int h, int mi) {
-            return *reinterpret_cast<const uint4*>(slot + a_row + mi * 2048 + (h == 0 ? co0 : co1));
-        };
-        auto rdB = [&](const unsigned char* slot, int h, int ni) {
-            return *reinterpret_cast<const uint4*>(slot + b_row + ni * 2048 + (h == 0 ? co0 : co1));
-        };
-        uint4 fa[MB], fb0[2], fb1[2];
-#define PV_ENC_PAIR(MI, FB)                                                                                  \
-        _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                     \
-            acc[MI][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(                                            \
-                __builtin_bit_cast(f16x8, fa[MI]), __builtin_bit_cast(f16x8, FB[ni]), acc[MI][ni], 0, 0, 0); \
-        __builtin_amdgcn_sched_barrier(0);
-#define PV_ENC_PSTEP(KT, CUR, NXT)                                                                           \
-        _Pragma("unroll") for (int mi = 0; mi < MB; ++mi) {                                                  \
-            PV_ENC_PAIR(mi, fb0)                                                                             \
-            fa[mi] = rdA(CUR, 1, mi);                                                                        \
-            if (mi == 1) { fb1[0] = rdB(CUR, 1, 0); fb1[1] = rdB(CUR, 1, 1); }                               \
-            __builtin_amdgcn_sched_barrier(0);                                                               \
-        }                                                                                                    \
-        __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * NPIECE));                                                   \
-        __builtin_amdgcn_s_barrier();                                                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-        _Pragma("unroll") for (int mi = 0; mi < MB; ++mi) {                                                  \
-            PV_ENC_PAIR(mi, fb1)                                                                             \
-            fa[mi] = rdA(NXT, 0, mi);                                                                        \
-            if (mi == 1) { fb0[0] = rdB(NXT, 0, 0); fb0[1] = rdB(NXT, 0, 1); }                               \
-            issue_piece((KT) + 4, CUR, mi);                                                                  \
-            __builtin_amdgcn_sched_barrier(0);                                                               \
+        for (int j = 0; j < 2; ++j) {
+            const int row = g.piece_row(lane, j);
+            kc[j] = R64::piece_col(lane, row);
+            offA[j] = (unsigned)(m0 + row) * ldaB + kc[j];
+            offB[j] = (n0 + row < p.N) ? (unsigned)(n0 + row) * p.ldb_bytes + kc[j] : kloop::DEAD;
         }
-        issue_all(0, ring0);
-        issue_all(1, ring1);
-        issue_all(2, ring2);
-        issue_all(3, ring3);
-        __builtin_amdgcn_s_waitcnt(0x0F70 | (3 * NPIECE));
-        __builtin_amdgcn_s_barrier();
+        if constexpr (LP == 0) {
+            const bool ktail = (Kb % 64) != 0;
+            auto issue = [&](int kt, unsigned char* slot) {
+                const unsigned kbase = (unsigned)kt * 64;
+                const bool dead = kt >= nk;
 #pragma unroll
-        for (int mi = 0; mi < MB; ++mi) fa[mi] = rdA(ring0, 0, mi);
-        fb0[0] = rdB(ring0, 0, 0); fb0[1] = rdB(ring0, 0, 1);
-        int kt = 0;
-        for (; kt + 4 <= nk; kt += 4) {
-            PV_ENC_PSTEP(kt, ring0, ring1)
-            PV_ENC_PSTEP(kt + 1, ring1, ring2)
-            PV_ENC_PSTEP(kt + 2, ring2, ring3)
-            PV_ENC_PSTEP(kt + 3, ring3, ring0)
+                for (int j = 0; j < 2; ++j)
+                    g.issue(rsA, rsB, slot, j, (dead | (ktail & (kbase + kc[j] >= Kb))) ? kloop::DEAD : offA[j] + kbase);
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    g.issue(rsA, rsB, slot, 2 + j,
+                            (dead | (offB[j] == kloop::DEAD) | (ktail & (kbase + kc[j] >= Kb))) ? kloop::DEAD : offB[j] + kbase);
+            };
+            KLOOP_RUN_FETCH_AFTER_BARRIER(kloop::F16, acc, g, ring0, ring1, ring2, ring3, nk, issue);
+        } else {
+            // whole 64-byte slabs only (the launcher checks K % 32 == 0)
+            const unsigned strideA = R64::PIECE_STRIDE * ldaB;
+            auto src = [&](int kt, int j) -> unsigned {
+                const unsigned kbase = (unsigned)kt * 64;
+                const bool dead = kt >= nk;
+                if (j < 2) return dead ? kloop::DEAD : offA[0] + ((unsigned)j * strideA + kbase);
+                const int jb = j >= 2 ? j - 2 : 0;
+                return (dead | (offB[jb] == kloop::DEAD)) ? kloop::DEAD : offB[jb] + kbase;
+            };
+            KLOOP_RUN_PIPELINED64(kloop::F16, MB, acc, g, rsA, rsB, ring0, ring1, ring2, ring3, nk, src);
         }
-        if (kt < nk) { PV_ENC_PSTEP(kt, ring0, ring1) }
-        if (kt + 1 < nk) { PV_ENC_PSTEP(kt + 1, ring1, ring2) }
-        if (kt + 2 < nk) { PV_ENC_PSTEP(kt + 2, ring2, ring3) }
-#undef PV_ENC_PSTEP
-#undef PV_ENC_PAIR
     } else {
-        // full-line form (gemm.hip, gemm_kernel_v7<..., LP = 2>): 128-byte K slabs = whole cache lines per DMA piece (8 rows x
-        // 128 B), two 64 KB slots, four 16-element k-steps per slab, the next slab's barrier before the last k-step, vmcnt(0)
-        // there (one slab of prefetch distance).  Whole 128-byte slabs only (the launcher checks K % 64 == 0).
-        constexpr int A2 = TM * 128, NP2 = MB + 4;
-        const int prow = lane >> 3;
-        const int psw = ((lane >> 4) + 4 * (wave & 1)) & 7;
-        const unsigned pcol = (unsigned)(((lane & 7) ^ psw) * 16);
-        const unsigned pA0 = (unsigned)(m0 + wave * 8 + prow) * (unsigned)p.lda * 2u + pcol;
-        const int brow0 = n0 + wave * 8 + prow;
-        const unsigned pB0 = (unsigned)brow0 * p.ldb_bytes + pcol;
-        const unsigned strideA = 64u * (unsigned)p.lda * 2u, strideB = 64u * p.ldb_bytes;
+        // whole 128-byte slabs only (the launcher checks K % 64 == 0)
+        const R128 g(lane, wave);
         const int nk2 = (int)(Kb / 128);
-        auto issue_piece2 = [&](int kt, unsigned char* slot, int j) {
+        const unsigned pA0 = (unsigned)(m0 + g.piece_row(lane)) * ldaB + g.piece_col(lane);
+        const int brow0 = n0 + g.piece_row(lane);
+        const unsigned pB0 = (unsigned)brow0 * p.ldb_bytes + g.piece_col(lane);
+        const unsigned strideA = R128::PIECE_STRIDE * ldaB, strideB = R128::PIECE_STRIDE * p.ldb_bytes;
+        auto src = [&](int kt, int j) -> unsigned {
             const unsigned kbase = (unsigned)kt * 128;
             const bool dead = kt >= nk2;
-            if (j < MB) {
-                const unsigned o = dead ? 0xffffff00u : pA0 + ((unsigned)j * strideA + kbase);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)(slot + (j * 8 + wave) * 1024), 16, o, 0, 0, 0);
-            } else {
-                const int jb = j - MB;
-                const unsigned o = (dead | (brow0 + jb * 64 >= p.N)) ? 0xffffff00u : pB0 + ((unsigned)jb * strideB + kbase);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(slot + A2 + (jb * 8 + wave) * 1024), 16, o, 0, 0, 0);
-            }
+            if (j < MB) return dead ? kloop::DEAD : pA0 + ((unsigned)j * strideA + kbase);
+            const int jb = j - MB;
+            return (dead | (brow0 + jb * R128::PIECE_STRIDE >= p.N)) ? kloop::DEAD : pB0 + ((unsigned)jb * strideB + kbase);
         };
-        const int fsw = (l31 >> 1) & 7;
-        const int a_row2 = (wm * 32 * MB + l31) * 128, b_row2 = A2 + (wn * 64 + l31) * 128;
-        int fco[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) fco[h] = ((2 * h + half) ^ fsw) * 16;
-        auto rdA2 = [&](const unsigned char* slot, int h, int mi) {
-            return *reinterpret_cast<const uint4*>(slot + a_row2 + mi * 4096 + fco[h]);
-        };
-        auto rdB2 = [&](const unsigned char* slot, int h, int ni) {
-            return *reinterpret_cast<const uint4*>(slot + b_row2 + ni * 4096 + fco[h]);
-        };
-        uint4 fa[MB], fb[2][2];
-#define PV_ENC_PAIR2(MI, H)                                                                                   \
-        _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                      \
-            acc[MI][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(                                             \
-                __builtin_bit_cast(f16x8, fa[MI]), __builtin_bit_cast(f16x8, fb[(H) & 1][ni]), acc[MI][ni], 0, 0, 0); \
-        __builtin_amdgcn_sched_barrier(0);
-#define PV_ENC_FSTEP(KT, CUR, NXT)                                                                            \
-        _Pragma("unroll") for (int h = 0; h < 4; ++h) {                                                       \
-            if (h == 3) {                                                                                     \
-                __builtin_amdgcn_s_waitcnt(0x0F70);                                                           \
-                __builtin_amdgcn_s_barrier();                                                                 \
-                __builtin_amdgcn_sched_barrier(0);                                                            \
-            }                                                                                                 \
-            _Pragma("unroll") for (int mi = 0; mi < MB; ++mi) {                                               \
-                PV_ENC_PAIR2(mi, h)                                                                           \
-                fa[mi] = h < 3 ? rdA2(CUR, h < 3 ? h + 1 : 0, mi) : rdA2(NXT, 0, mi);                         \
-                if (mi == 1) {                                                                                \
-                    fb[(h + 1) & 1][0] = h < 3 ? rdB2(CUR, h < 3 ? h + 1 : 0, 0) : rdB2(NXT, 0, 0);           \
-                    fb[(h + 1) & 1][1] = h < 3 ? rdB2(CUR, h < 3 ? h + 1 : 0, 1) : rdB2(NXT, 0, 1);           \
-                }                                                                                             \
-                if (h == 3) issue_piece2((KT) + 2, CUR, mi);                                                  \
-                if (h == 0) {                                                                                 \
-                    _Pragma("unroll") for (int jb = mi; jb < 4; jb += MB) issue_piece2((KT) + 1, NXT, MB + jb); \
-                }                                                                                             \
-                __builtin_amdgcn_sched_barrier(0);                                                            \
-            }                                                                                                 \
-        }
-#pragma unroll
-        for (int j = 0; j < NP2; ++j) issue_piece2(0, ring0, j);
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        __builtin_amdgcn_s_barrier();
-#pragma unroll
-        for (int j = 0; j < MB; ++j) issue_piece2(1, ring1, j);
-#pragma unroll
-        for (int mi = 0; mi < MB; ++mi) fa[mi] = rdA2(ring0, 0, mi);
-        fb[0][0] = rdB2(ring0, 0, 0); fb[0][1] = rdB2(ring0, 0, 1);
-        int kt = 0;
-        for (; kt + 2 <= nk2; kt += 2) {
-            PV_ENC_FSTEP(kt, ring0, ring1)
-            PV_ENC_FSTEP(kt + 1, ring1, ring0)
-        }
-        if (kt < nk2) { PV_ENC_FSTEP(kt, ring0, ring1) }
-#undef PV_ENC_FSTEP
-#undef PV_ENC_PAIR2
+        KLOOP_RUN_FULL_LINE(kloop::F16, MB, acc, g, rsA, rsB, ring0, ring1, nk2, src);
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0): drain the off-the-end prefetches (and the threshold DMA)
     __syncthreads();
