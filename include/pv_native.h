@@ -45,8 +45,9 @@ extern "C" {
 /* ABI version; bumped on any struct / signature / flag change (10: PV_SAE_SPARSE_GRADS, pv_sae_tp_partial / pv_sae_tp_finish;
  * 11: pv_sae_tp_merge / pv_sae_tp_bucket_*, pv_build_id, the dense ReLU + L1 step pv_sae_dense_*; 17: pv_gemm_epilogue, the
  * gemm_persist / gemm_stagger tuning keys; 22: pv_sae_desc.activation / lp_norm,
- * normalize_layer_norm = 2 (constant_norm_rescale), the split-fp16 dense GEMMs and their tuning key dense_fp32, gemm_cus). */
-#define PV_ABI_VERSION 23
+ * normalize_layer_norm = 2 (constant_norm_rescale), the split-fp16 dense GEMMs and their tuning key dense_fp32, gemm_cus;
+ * 24: pv_vit_desc.pooling, PV_ATTN_MAX_TOKENS = 2048 (was 640)). */
+#define PV_ABI_VERSION 24
 int pv_abi_version(void);
 /* Hash of the sources this binary was built from (sha256 over the .hip / .hpp files of vit_prisma_amd/csrc and this header, names and
  * contents, sorted; first 32 hex digits): the prebuilt library travels next to the sources, and the Python binding refuses
@@ -60,10 +61,21 @@ void pv_last_error(char* buf, size_t len);
 /* of prisma_tools/hooked_root_module.py:289-332 fused in as tap stores)                        */
 /* ------------------------------------------------------------------------------------------ */
 
+/* Largest n_tokens the attention kernels serve (d_head 32 or 64): THE cap -- pv_vit_plan_create, the attention launchers and the
+ * Python binding (_native.ATTN_MAX_TOKENS, NativeViT.supported) all state and enforce this number.  2048 covers 224 px / 8 (785),
+ * 448 px / 16 (785) and 448 - 518 px / 14 (1025 - 1370) with room to spare; it is a stated cap, not a hardware limit. */
+#define PV_ATTN_MAX_TOKENS 2048
+
+/* What the final stage feeds the head with (classification_type and the dino-vitb special case, models/base_vit.py:195-208). */
+#define PV_POOL_CLS 0         /* the CLS row of ln_final                       base_vit.py:199, 207                     */
+#define PV_POOL_MEAN 1        /* "gaap": the mean over ALL tokens of ln_final  base_vit.py:195-197                      */
+#define PV_POOL_CLS_MEAN 2    /* dino-vitb: cat(cls, mean(patch tokens)) -> [B, d_model, 2]; without head only
+                               * (F.normalize then acts over that last dimension of size 2)  base_vit.py:199-206      */
+
 typedef struct pv_vit_desc {
     int32_t n_layers, d_model, n_heads, d_head, d_mlp;
     int32_t n_channels, patch_size, image_size;
-    int32_t n_tokens;          /* patches (+1 with cls token)                                 */
+    int32_t n_tokens;          /* patches (+1 with cls token); <= PV_ATTN_MAX_TOKENS          */
     int32_t n_classes;         /* head width; ignored when has_head == 0                      */
     int32_t use_cls_token;     /* models/base_vit.py:171-175                                  */
     int32_t layer_norm_pre;    /* models/base_vit.py:183-185                                  */
@@ -73,6 +85,7 @@ typedef struct pv_vit_desc {
     int32_t dtype;             /* PV_DTYPE_*: storage dtype of params, residual stream, taps  */
     float eps;                 /* LayerNorm eps, models/layers/layer_norm.py:88               */
     float attn_scale;          /* sqrt(d_head) or 1, models/layers/attention.py:96-99         */
+    int32_t pooling;           /* PV_POOL_*, models/base_vit.py:195-208                       */
 } pv_vit_desc;
 
 /* Parameters in the reference's own layouts (the state-dict layout produced by
@@ -112,7 +125,7 @@ enum pv_slot {
     PV_SLOT_LNF_SCALE = 5,    /* ln_final.hook_scale                [B, T, 1]    f32          */
     PV_SLOT_LNF_NORM_F32 = 6, /* ln_final.hook_normalized (bf16 mode) [B, T, d]  f32          */
     PV_SLOT_LNF_OUT = 7,      /* hook_ln_final                      [B, T, d]    T            */
-    PV_SLOT_HEAD_OUT = 8,     /* hook_post_head_pre_normalize       [B, n_cls] or [B, d]  T   */
+    PV_SLOT_HEAD_OUT = 8,     /* hook_post_head_pre_normalize  [B, n_cls] or [B, d] ([B, d, 2]: PV_POOL_CLS_MEAN) T */
     /* per-layer slots */
     PV_SLOT_LN1_SCALE = 16,   /* blocks.l.ln1.hook_scale            [B, T, 1]    f32          */
     PV_SLOT_LN1_NORM_F32 = 17,
@@ -165,9 +178,9 @@ size_t pv_vit_workspace_bytes(const pv_vit_plan* plan, int32_t batch);
  *   n_blocks       number of transformer blocks to run: n_layers for a full forward, k for
  *                  stop_at_layer=k (the caller resolves negative indices, base_vit.py:187)
  *   run_head       0: stop after the blocks (stop_at_layer semantics, base_vit.py:189-190; the
- *                  caller taps the last residual), 1: ln_final + cls + head (+normalise) -> out
+ *                  caller taps the last residual), 1: ln_final + pooling (desc.pooling) + head (+normalise) -> out
  *   taps           HOST array; buffers not listed are kept in the workspace or never materialised
- *   out            [B, n_classes] (or [B, d] without head) T; may be NULL when run_head == 0
+ *   out            [B, n_classes] (or [B, d] without head; [B, d, 2] with PV_POOL_CLS_MEAN) T; may be NULL when run_head == 0
  */
 int pv_vit_forward(pv_vit_plan* plan, const void* images, int32_t batch, int32_t n_blocks,
                    int32_t run_head, const pv_tap* taps, int32_t n_taps, void* workspace,

@@ -11,7 +11,9 @@ from typing import Optional
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PV_NATIVE_LIB") or os.path.join(HERE, "libpvnative.so")     # (override: kernel A/B builds)
-ABI_VERSION = 23
+ABI_VERSION = 24
+ATTN_MAX_TOKENS = 2048            # PV_ATTN_MAX_TOKENS of include/pv_native.h (held equal by tests/test_dino_cpu.py)
+PV_POOL_CLS, PV_POOL_MEAN, PV_POOL_CLS_MEAN = 0, 1, 2
 
 PV_DTYPE_F32, PV_DTYPE_BF16 = 0, 1
 PV_ACT = {"gelu": 0, "quick_gelu": 1, "relu": 2}
@@ -34,7 +36,7 @@ class VitDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_layers", "d_model", "n_heads", "d_head", "d_mlp", "n_channels", "patch_size", "image_size",
         "n_tokens", "n_classes", "use_cls_token", "layer_norm_pre", "has_head", "normalize_output",
-        "activation", "dtype")] + [("eps", C.c_float), ("attn_scale", C.c_float)]
+        "activation", "dtype")] + [("eps", C.c_float), ("attn_scale", C.c_float), ("pooling", C.c_int32)]
 
 
 class VitLayerWeights(C.Structure):

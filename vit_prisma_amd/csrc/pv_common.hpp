@@ -34,6 +34,8 @@ void pv_set_error(const std::string& msg);
             return PV_ERR_HIP;                                                            \
         }                                                                                 \
     } while (0)
+#define PV_STR_(x) #x
+#define PV_STR(x) PV_STR_(x)            /* a macro's VALUE as a string literal (error texts that state PV_ATTN_MAX_TOKENS) */
 #define PV_REQUIRE(cond, msg)                                                             \
     do {                                                                                  \
         if (!(cond)) {                                                                    \

@@ -96,6 +96,47 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const T* __restrict__ x, T*
     }
 }
 
+// Pooled final stages (models/base_vit.py:195-208): out[b][c] = mean over tokens t0 .. T - 1 of x[b][t][c] -- t0 = 0: "gaap", the mean
+// over all tokens of ln_final; t0 = 1 with PAIR: the dino-vitb output [B, d, 2] = (x[b][0][c], mean over the patch tokens) written as
+// one pair per column.  A workgroup owns 128 columns of one image: lane = two adjacent columns (one 4- / 8-byte load per token row,
+// 256 / 512 contiguous bytes per wave), wave w sums the tokens t0 + w, t0 + w + 4, ... in fp32, the four partial sums meet in LDS in a
+// fixed order (the same bits every run) and are rounded ONCE to the storage dtype.  Stores: 2 (PAIR: 4) consecutive elements per lane,
+// contiguous over d_model.  d % 2 == 0.  HBM-bound on one read of x; 1 KiB of LDS, no design occupancy beyond ln_kernel's 6 waves per
+// SIMD (tests/test_attention_long_resources_cpu.py).
+template <typename T, bool PAIR>
+__global__ __launch_bounds__(256) void token_mean_kernel(const T* __restrict__ x, T* __restrict__ out, int Tn, int d, int t0) {
+    __shared__ float part[4][128];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.y, c = blockIdx.x * 128 + 2 * lane;
+    const T* xb = x + (int64_t)b * Tn * d;
+    float s0 = 0.f, s1 = 0.f;
+    if (c < d) {
+        for (int t = t0 + wave; t < Tn; t += 4) {
+            const T* r = xb + (int64_t)t * d + c;
+            s0 += DT<T>::load(r);
+            s1 += DT<T>::load(r + 1);
+        }
+    }
+    part[wave][2 * lane] = s0;
+    part[wave][2 * lane + 1] = s1;
+    __syncthreads();
+    if (wave != 0 || c >= d) return;
+    const float inv_n = 1.0f / (float)(Tn - t0);
+    const float m0 = (((part[0][2 * lane] + part[1][2 * lane]) + part[2][2 * lane]) + part[3][2 * lane]) * inv_n;
+    const float m1 = (((part[0][2 * lane + 1] + part[1][2 * lane + 1]) + part[2][2 * lane + 1]) + part[3][2 * lane + 1]) * inv_n;
+    if constexpr (PAIR) {
+        T* o = out + ((int64_t)b * d + c) * 2;
+        o[0] = xb[c];
+        DT<T>::store(o + 1, m0);
+        o[2] = xb[c + 1];
+        DT<T>::store(o + 3, m1);
+    } else {
+        T* o = out + (int64_t)b * d + c;
+        DT<T>::store(o, m0);
+        DT<T>::store(o + 1, m1);
+    }
+}
+
 // out[b][c][r] = in[b][r][c]; 32 x 32 tiles through LDS (+1 pad), coalesced on both sides
 template <typename E>
 __global__ __launch_bounds__(256) void transpose_kernel(const E* __restrict__ in, E* __restrict__ out, int R, int C) {
@@ -146,6 +187,23 @@ int pv_launch_l2norm(int dtype, const void* x, void* out, int rows, int n, hipSt
     else
         hipLaunchKernelGGL((l2norm_kernel<float>), grid, block, 0, stream, (const float*)x, (float*)out, rows, n);
     PV_LAUNCH_CHECK("l2norm_kernel");
+    return PV_OK;
+}
+
+int pv_launch_token_mean(int dtype, const void* x, void* out, int B, int T, int d, int t0, int pair, hipStream_t stream) {
+    PV_REQUIRE(x && out && B > 0 && B <= 65535 && d > 0 && d % 2 == 0, "token mean: operands");
+    PV_REQUIRE(t0 >= 0 && t0 < T, "token mean: empty token range");
+    const dim3 grid((d + 127) / 128, B), block(256);
+    const double eb = dtype == PV_DTYPE_BF16 ? 2.0 : 4.0;
+    ProfScope prof(PV_PROF_LN, stream, (double)B * (T - t0) * d, ((double)B * (T - t0) * d + (double)B * d * (pair ? 2 : 1)) * eb);
+    if (dtype == PV_DTYPE_BF16) {
+        if (pair) hipLaunchKernelGGL((token_mean_kernel<bf16_t, true>), grid, block, 0, stream, (const bf16_t*)x, (bf16_t*)out, T, d, t0);
+        else hipLaunchKernelGGL((token_mean_kernel<bf16_t, false>), grid, block, 0, stream, (const bf16_t*)x, (bf16_t*)out, T, d, t0);
+    } else {
+        if (pair) hipLaunchKernelGGL((token_mean_kernel<float, true>), grid, block, 0, stream, (const float*)x, (float*)out, T, d, t0);
+        else hipLaunchKernelGGL((token_mean_kernel<float, false>), grid, block, 0, stream, (const float*)x, (float*)out, T, d, t0);
+    }
+    PV_LAUNCH_CHECK("token_mean_kernel");
     return PV_OK;
 }
 

@@ -26,6 +26,9 @@ int pv_launch_ln(int dtype, const LnParams& p, hipStream_t stream);
 // hook_normalized tensor (pv_vit_forward_stage, PV_STAGE_LN1 / PV_STAGE_LN2).  n % 4 == 0.
 int pv_launch_cast_from_f32(int dtype, const float* in, void* out, int64_t n, hipStream_t stream);
 int pv_launch_l2norm(int dtype, const void* x, void* out, int rows, int n, hipStream_t stream);
+// x [B][T][d] (the ln_final output) -> mean over tokens t0 .. T - 1, fp32 accumulation, one rounding (models/base_vit.py:195-208):
+// pair == 0: out [B][d] ("gaap" with t0 = 0); pair == 1: out [B][d][2] = (x[b][0][c], mean) -- the dino-vitb output (t0 = 1)
+int pv_launch_token_mean(int dtype, const void* x, void* out, int B, int T, int d, int t0, int pair, hipStream_t stream);
 int pv_launch_transpose(int elem_bytes, const void* in, void* out, int batch, int R, int C, hipStream_t stream);
 // bf16 NCHW images -> [B*G*G][Kp] patch rows (im2col once per batch, zero-padded to Kp columns), and the matching row padding
 // of the [d][K] patch-embedding weights: the operands of the tiled GEMM for patch sizes its in-kernel gather does not cover

@@ -56,7 +56,10 @@ extern "C" int pv_vit_plan_create(const pv_vit_desc* desc, pv_vit_plan** out_pla
     const int G = d.image_size / d.patch_size;
     const int P = G * G;
     PV_REQUIRE(d.n_tokens == P + (d.use_cls_token ? 1 : 0), "n_tokens != patches (+cls)");
-    PV_REQUIRE(pv_attention_supported(d.n_tokens, d.d_head), "attention shape unsupported (T <= 640, d_head in {32,64})");
+    PV_REQUIRE(pv_attention_supported(d.n_tokens, d.d_head), "attention shape unsupported (T <= " PV_STR(PV_ATTN_MAX_TOKENS) ", d_head in {32,64})");
+    PV_REQUIRE(d.pooling >= PV_POOL_CLS && d.pooling <= PV_POOL_CLS_MEAN, "pooling");
+    // cat(cls, mean(patches)) is [B, d_model, 2]: the reference's registry has it without a head only (base_vit.py:199-208)
+    PV_REQUIRE(d.pooling != PV_POOL_CLS_MEAN || (!d.has_head && d.n_tokens >= 2), "PV_POOL_CLS_MEAN needs has_head == 0 and a patch token");
     PV_REQUIRE(d.activation >= PV_ACT_GELU && d.activation <= PV_ACT_RELU, "activation");
     if (d.has_head) PV_REQUIRE(d.n_classes > 0, "n_classes");
     pv_vit_plan* p = new pv_vit_plan();
@@ -150,7 +153,7 @@ extern "C" int pv_vit_plan_set_weights(pv_vit_plan* p, const pv_vit_weights* w, 
 namespace {
 struct Workspace {
     size_t total;
-    size_t embed, resid_a, resid_b, ln_out, q, k, v, z, resid_mid, mlp_post, lnf, head, patches;
+    size_t embed, resid_a, resid_b, ln_out, q, k, v, z, resid_mid, mlp_post, lnf, head, pooled, patches;
 };
 Workspace carve(const pv_vit_plan* p, int B) {
     const pv_vit_desc& d = p->d;
@@ -170,7 +173,8 @@ Workspace carve(const pv_vit_plan* p, int B) {
     w.resid_mid = take(M * d.d_model);
     w.mlp_post = take(M * d.d_mlp);
     w.lnf = take(M * d.d_model);
-    w.head = take((size_t)B * (d.has_head ? d.n_classes : d.d_model));
+    w.head = take((size_t)B * (d.has_head ? d.n_classes : d.d_model * (d.pooling == PV_POOL_CLS_MEAN ? 2 : 1)));
+    w.pooled = take((size_t)B * d.d_model);
     w.patches = p->patch_prepack ? take((size_t)B * p->P * p->Kp) : 0;
     w.total = off + 256;
     return w;
@@ -485,8 +489,8 @@ int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, c
     }
     if (!run_head) return PV_OK;
 
-    // ---- ln_final on all tokens only if one of its taps is requested, else on the CLS rows only
-    const bool lnf_all = tap_at(PV_SLOT_LNF_SCALE, 0) || tap_at(PV_SLOT_LNF_NORM_F32, 0) || tap_at(PV_SLOT_LNF_OUT, 0);
+    // ---- ln_final on all tokens only if one of its taps is requested or the pooling reads them all, else on the CLS rows only
+    const bool lnf_all = d.pooling != PV_POOL_CLS || tap_at(PV_SLOT_LNF_SCALE, 0) || tap_at(PV_SLOT_LNF_NORM_F32, 0) || tap_at(PV_SLOT_LNF_OUT, 0);
     void* lnf = pick(PV_SLOT_LNF_OUT, 0, ws.lnf);
     int64_t lnf_ld;   // row stride (elements) between CLS rows of consecutive images
     {
@@ -504,21 +508,30 @@ int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, c
         L.out = lnf;
         if ((rc = pv_launch_ln(dt, L, stream))) return rc;
     }
-    // ---- cls row -> head (head.py:27-37) -> hook_post_head_pre_normalize -> F.normalize
-    const int nout = d.has_head ? d.n_classes : dm;
+    // ---- pooled row (base_vit.py:195-208) -> head (head.py:27-37) -> hook_post_head_pre_normalize -> F.normalize
+    const bool cls_mean = d.pooling == PV_POOL_CLS_MEAN;
+    const int nout = d.has_head ? d.n_classes : (cls_mean ? 2 * dm : dm);
     void* head_tap = tap_at(PV_SLOT_HEAD_OUT, 0);
     void* hb = head_tap ? head_tap : (d.normalize_output ? (void*)(wsb + ws.head) : out);
+    if (d.pooling != PV_POOL_CLS) {
+        // "gaap": the mean over all tokens feeds the head (or IS the output); dino-vitb: [B, d, 2] = (cls, mean over the patches)
+        void* pooled = (d.has_head) ? (void*)(wsb + ws.pooled) : hb;
+        if ((rc = pv_launch_token_mean(dt, lnf, pooled, B, T, dm, cls_mean ? 1 : 0, cls_mean ? 1 : 0, stream))) return rc;
+        lnf = pooled;
+        lnf_ld = dm;
+    }
     if (d.has_head) {
         GemmParams g = {};
         g.A = lnf; g.lda = lnf_ld; g.a_mode = PV_A_PLAIN; g.Bt = p->WhT; g.ldb = dm;
         g.M = B; g.N = nout; g.K = dm; g.epi = PV_EPI_BIAS; g.bias0 = p->w.b_H; g.out0 = hb; g.ldo = nout;
         if ((rc = pv_launch_gemm(dt, g, stream))) return rc;
-    } else {
+    } else if (d.pooling == PV_POOL_CLS) {
         PV_HIP_CHECK(hipMemcpy2DAsync(hb, (size_t)dm * p->EB, lnf, (size_t)lnf_ld * p->EB, (size_t)dm * p->EB, B,
                                       hipMemcpyDeviceToDevice, stream));
     }
     if (d.normalize_output) {
-        if ((rc = pv_launch_l2norm(dt, hb, out, B, nout, stream))) return rc;
+        // dim = -1 of [B, d, 2] is the (cls, mean) pair of one channel (base_vit.py:214-215 on the concatenated tensor)
+        if ((rc = cls_mean ? pv_launch_l2norm(dt, hb, out, B * dm, 2, stream) : pv_launch_l2norm(dt, hb, out, B, nout, stream))) return rc;
     } else if (hb != out) {
         PV_HIP_CHECK(hipMemcpyAsync(out, hb, (size_t)B * nout * p->EB, hipMemcpyDeviceToDevice, stream));
     }

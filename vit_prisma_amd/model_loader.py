@@ -3,7 +3,7 @@
 
 The reference resolves ``model_name`` to a config and to weights by downloading from HuggingFace (model_loader.py:397-407, 775-784);
 there is no network here.  This loader therefore takes the config from the architecture tables of ``synth.ARCHS`` plus the
-per-name overrides of the reference registry (``NAME_OVERRIDES``) -- what ``load_config`` would have produced for these names, SURVEY.md 8a -- and the weights from a LOCAL open_clip / HuggingFace CLIP checkpoint
+per-name overrides of the reference registry (``NAME_OVERRIDES``) -- what ``load_config`` would have produced for these names, SURVEY.md 8a -- and the weights from a LOCAL open_clip / HuggingFace CLIP checkpoint, or for the DINO names (``DINO_ARCH``) a HuggingFace ``ViTModel`` one
 (``local_path=...``: a ``.safetensors`` / ``.pt`` / ``.bin`` file, converted by ``weights.py`` exactly as the reference's converters do) --
 or none (``pretrained=False``: the reference's initialisation).  Everything else about the signature is the reference's; the options
 that rewrite weights (``fold_ln``, ``center_writing_weights``, ``refactor_factored_attn_matrices``) are not implemented and raise
@@ -20,7 +20,7 @@ import torch
 from .configs import HookedViTConfig
 from .synth import ARCHS
 from .vit import HookedViT
-from .weights import load_clip_vision_weights
+from .weights import load_clip_vision_weights, load_dino_weights
 
 # reference model names (model_loader.py:97-123) -> architecture table
 MODEL_ARCH = {
@@ -38,18 +38,27 @@ MODEL_ARCH = {
 NAME_OVERRIDES = {
     "openai/clip-vit-base-patch32": {"eps": 1e-6, "normalize_output": False},
 }
+# the DINO family (registry DINO_CONFIGS, :544-570): HuggingFace ViTModel checkpoints, converted by weights.convert_dino_weights.  The
+# registry's fields for these names are pinned by tests/golden/model_registry_dino.json (tests/golden/gen_golden_dino.py).  The vitb
+# names return cat(cls, mean(patches)) -- [B, 768, 2] (base_vit.py:199-206).
+DINO_ARCH = {
+    "facebook/dino-vitb16": "dino-vitb16",
+    "facebook/dino-vitb8": "dino-vitb8",
+    "facebook/dino-vits16": "dino-vits16",
+    "facebook/dino-vits8": "dino-vits8",
+}
 DTYPE_FROM_STRING = {"float32": torch.float32, "fp32": torch.float32, "float16": torch.float16, "fp16": torch.float16,
                      "bfloat16": torch.bfloat16, "bf16": torch.bfloat16}
 
 
 def list_available_models():
-    return sorted(MODEL_ARCH)
+    return sorted({**MODEL_ARCH, **DINO_ARCH})
 
 
 def load_config(model_name: str, dtype: torch.dtype = torch.float32, device: str = "cuda", **overrides) -> HookedViTConfig:
-    if model_name not in MODEL_ARCH:
+    if model_name not in MODEL_ARCH and model_name not in DINO_ARCH:
         raise ValueError(f"{model_name!r}: offline build knows {list_available_models()} (no network: configs cannot be downloaded)")
-    kw = dict(ARCHS[MODEL_ARCH[model_name]])
+    kw = dict(ARCHS[MODEL_ARCH.get(model_name) or DINO_ARCH[model_name]])
     kw["model_name"] = model_name
     kw.update(NAME_OVERRIDES.get(model_name, {}))
     kw.update(overrides)
@@ -77,7 +86,10 @@ def load_hooked_model(model_name: str, model_class: Optional[Type] = None, model
         if local_path is None:
             raise FileNotFoundError(f"pretrained=True needs local_path=<checkpoint file> for {model_name!r}: this build cannot download "
                                     "weights (no network); pass pretrained=False for the reference's random initialisation")
-        load_clip_vision_weights(model, local_path, fold_value_biases=bool(fold_value_biases))
+        if model_name in DINO_ARCH:
+            load_dino_weights(model, local_path, fold_value_biases=bool(fold_value_biases))
+        else:
+            load_clip_vision_weights(model, local_path, fold_value_biases=bool(fold_value_biases))
     model = model.to(dtype)
     if move_to_device:
         model = model.to(device)

@@ -12,7 +12,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import torch
 
 from . import _native as N
-from .tap_plan import TapSpec, final_residual_name, hook_order, tap_spec
+from .tap_plan import TapSpec, final_residual_name, head_out_shape, hook_order, pooling_mode, tap_spec
 
 _ALIGN = 256
 _ESIZE = {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2}
@@ -120,7 +120,8 @@ class NativeViT:
             activation=N.PV_ACT[cfg.activation_name],
             dtype=N.PV_DTYPE_BF16 if cfg.dtype == torch.bfloat16 else N.PV_DTYPE_F32,
             eps=float(cfg.eps),
-            attn_scale=float(cfg.d_head ** 0.5) if cfg.use_attn_scale else 1.0)
+            attn_scale=float(cfg.d_head ** 0.5) if cfg.use_attn_scale else 1.0,
+            pooling=pooling_mode(cfg))
         self._plan = C.c_void_p()
         N.check(self.lib.pv_vit_plan_create(C.byref(desc), C.byref(self._plan)), "pv_vit_plan_create")
         self._shadow: Optional[torch.Tensor] = None
@@ -156,14 +157,19 @@ class NativeViT:
             return f"normalization_type {cfg.normalization_type}"
         if cfg.activation_name not in N.PV_ACT:
             return f"activation {cfg.activation_name}"
-        if cfg.classification_type != "cls" or "dino-vitb" in str(cfg.model_name):
+        if cfg.classification_type not in ("cls", "gaap"):
             return "classification_type"
+        if pooling_mode(cfg) == N.PV_POOL_CLS_MEAN and cfg.return_type != "pre_logits":
+            # [B, d_model, 2] @ W_H: no entry of the reference's registry has it; the plan builds the concatenation without a head only
+            return "classification_type: the dino-vitb concatenation (cls, mean of patches) with a head stays on the PyTorch path"
         if getattr(cfg, "is_video_transformer", False) or getattr(cfg, "use_bert_block", False) or cfg.attn_only:
             return "architecture variant"
         if cfg.d_model % 8 or cfg.d_mlp % 8 or cfg.d_model > 2048:
             return "d_model/d_mlp alignment"
-        if n_tokens > 640 or cfg.d_head not in (32, 64):
+        if n_tokens > N.ATTN_MAX_TOKENS or cfg.d_head not in (32, 64):
             return "attention shape"
+        if pooling_mode(cfg) == N.PV_POOL_CLS_MEAN and n_tokens < 2:
+            return "classification_type: no patch token to average"
         if cfg.attn_dropout_rate or cfg.mlp_dropout_rate:
             return None  # dropout is the identity in eval mode; training mode is checked by the caller
         return None
@@ -355,13 +361,16 @@ class NativeViT:
                     nbytes *= dim
                 offsets[key] = (total, s)
                 total += (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
-        n_out = cfg.n_classes if cfg.return_type != "pre_logits" else cfg.d_model
+        out_shape = head_out_shape(cfg, B)
         if layout is not None:
             out_off, total = layout[4], layout[5]
         else:
             out_off = total
             if run_head:
-                total += (B * n_out * images.element_size() + _ALIGN - 1) // _ALIGN * _ALIGN
+                nbytes = images.element_size()
+                for dim in out_shape:
+                    nbytes *= dim
+                total += (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
             if lkey is not None:
                 if len(self._layouts) >= 16:
                     self._layouts.pop(next(iter(self._layouts)))
@@ -436,7 +445,7 @@ class NativeViT:
                     t = t.to(cache_device)
             cache[n] = t[0] if remove_batch_dim else t
         if run_head:
-            out = view(slab, out_off, cfg.dtype, (B, n_out))
+            out = view(slab, out_off, cfg.dtype, out_shape)
         elif (specs[out_name].slot, specs[out_name].layer) in external:
             out = external[(specs[out_name].slot, specs[out_name].layer)]
         else:

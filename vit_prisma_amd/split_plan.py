@@ -324,7 +324,11 @@ class _Run:
                 if cfg.classification_type == "gaap":
                     x = x.mean(dim=1)
                 elif cfg.classification_type == "cls":
-                    x = x[:, 0]
+                    cls_tok = x[:, 0]
+                    if "dino-vitb" in cfg.model_name:
+                        x = torch.cat((cls_tok.unsqueeze(-1), x[:, 1:].mean(dim=1).unsqueeze(-1)), dim=-1)
+                    else:
+                        x = cls_tok
                 if cfg.return_type != "pre_logits":
                     x = model.head(x)
                 model.hook_post_head_pre_normalize(x)                # observe-only

@@ -1,4 +1,4 @@
-"""Real-weight loading for the two target architectures from LOCAL checkpoints (there is no network
+"""Real-weight loading for the target architectures (CLIP B/32, L/14@336; DINO ViT-B/S) from LOCAL checkpoints (there is no network
 on the build or GPU boxes, so nothing here downloads).
 
 ``convert_open_clip_weights`` / ``convert_hf_clip_weights`` produce the Prisma state-dict layout
@@ -84,6 +84,27 @@ def convert_hf_clip_weights(old_state_dict: Mapping[str, torch.Tensor], cfg: Hoo
     return new
 
 
+def convert_dino_weights(old_state_dict: Mapping[str, torch.Tensor], cfg: HookedViTConfig) -> Dict[str, torch.Tensor]:
+    """HuggingFace ``ViTModel`` (facebook/dino-vit{b,s}{16,8}): ``embeddings.*``, ``encoder.layer.N.*``, ``layernorm.*`` -- the key
+    mapping of the reference's converter of the same name (models/weight_conversion.py:432-518).  A DINO backbone has no pre-LayerNorm
+    and no head, and its patch convolution has a bias; cls_token [1,1,d] and position_embeddings [1,T,d] come in HF's own shapes."""
+    sd = old_state_dict
+    new: Dict[str, torch.Tensor] = {
+        "cls_token": sd["embeddings.cls_token"],
+        "pos_embed.W_pos": sd["embeddings.position_embeddings"].squeeze(0),
+        "embed.proj.weight": sd["embeddings.patch_embeddings.projection.weight"],
+        "embed.proj.bias": sd["embeddings.patch_embeddings.projection.bias"],
+        "ln_final.w": sd["layernorm.weight"], "ln_final.b": sd["layernorm.bias"],
+    }
+    for layer in range(cfg.n_layers):
+        old = f"encoder.layer.{layer}"
+        a = old + ".attention.attention"
+        new.update(_block(sd, cfg, f"blocks.{layer}", sd[a + ".query.weight"], sd[a + ".key.weight"], sd[a + ".value.weight"],
+                          sd[a + ".query.bias"], sd[a + ".key.bias"], sd[a + ".value.bias"], old + ".attention.output.dense", None,
+                          old + ".layernorm_before", old + ".layernorm_after", old + ".intermediate.dense", old + ".output.dense"))
+    return new
+
+
 def read_checkpoint(path: str) -> Dict[str, torch.Tensor]:
     """A local ``.safetensors`` / ``.pt`` / ``.bin`` file -> flat state dict (``state_dict`` / ``model`` wrappers unwrapped)."""
     if not os.path.isfile(path):
@@ -116,4 +137,22 @@ def load_clip_vision_weights(model, path: str, source: Optional[str] = None, fol
     if fold_value_biases:
         new = model.fold_value_biases(new)
     model.load_state_dict(new, strict=True)
+    return model
+
+
+def load_dino_weights(model, path: str, fold_value_biases: bool = False):
+    """Load a local HuggingFace DINO ``ViTModel`` checkpoint (keys ``embeddings.*`` / ``encoder.layer.N.*`` / ``layernorm.*``, with or
+    without a leading ``vit.``) into a ``HookedViT`` built for the matching architecture; the model's own ``head`` parameters (unused:
+    the DINO configs return pre_logits) keep their values.  Returns the model."""
+    sd = read_checkpoint(path)
+    sd = {k[len("vit."):] if k.startswith("vit.") else k: v for k, v in sd.items()}
+    if "embeddings.cls_token" not in sd:
+        raise ValueError("unrecognised checkpoint layout (expected HuggingFace ViTModel 'embeddings.*' / 'encoder.layer.*' keys)")
+    dtype = next(model.parameters()).dtype
+    new = {k: v.to(dtype) for k, v in convert_dino_weights(sd, model.cfg).items()}
+    if fold_value_biases:
+        new = model.fold_value_biases(new)
+    missing, unexpected = model.load_state_dict(new, strict=False)
+    if unexpected or any(not k.startswith("head.") for k in missing):
+        raise ValueError(f"checkpoint does not match the model: missing {missing}, unexpected {unexpected}")
     return model
