@@ -10,6 +10,10 @@
 //   gemm_kernel_v7   bf16, ONE 512-thread workgroup per CU, (64*MB) x 256 tile, template parameter LP = K-loop form:
 //                    0 barrier-then-fetch (patch gather, K tails), 1 software-pipelined 64-byte slabs, 2 full-line 128-byte slabs.
 //   gemm_kernel_v8   v7's full-line form made persistent: a workgroup walks its tiles, their K slabs one stream.
+// bf16 in v4 / v7 / v8 multiplies on v_mfma_f32_16x16x32_bf16 (the higher clock under the power cap, DESIGN.md 3.6;
+// -DPV_GEMM_MFMA=32: the 32x32x16 shape in all three, for A/B builds); every one of them accumulates an output in 32-element groups
+// of k in rising order, so results do not depend on the kernel picked.  gemm_kernel stays on 32x32x16 (it serves only shapes the
+// others cannot take).
 // The K loops of v7 and v8 -- slot geometry, swizzles, step bodies, drivers -- and the XCD-aware tile order live in kloop.hpp,
 // shared with the SAE filter GEMM (sae_enc.hip); the kernels here keep their LDS objects, descriptors, piece sources and epilogues.
 #include <atomic>
@@ -452,6 +456,33 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
 //   * epilogue staged through LDS in two 32-row halves per wave (34.8 KB <= the ring) 
 // ---------------------------------------------------------------------------------------------------
 using kloop::lds_ptr_t;
+// The MFMA shape of the bf16 kernels v4 / v7 / v8 (kloop.hpp: 16x16x32 unless built with -DPV_GEMM_MFMA=32) and what it does to
+// their store epilogues.  These transpose a 32-row block of the wave's accumulators through LDS in four PASSES of 8 rows x 64
+// columns; in a pass lane l stores the 8-column chunk l & 7 of the pass's row l >> 3.  With 32x32x16 accumulators a pass is 8
+// consecutive rows.  With 16x16x32 ones (row = 4 * (lane >> 4) + reg inside a 16-row block) a pass takes register pair
+// 2 * (it & 1) of block it >> 1 from every lane, so that all 64 lanes stage 8 values per pass as before: its rows are
+// 16 * (it >> 1) + 2 * (it & 1) + {0, 1, 4, 5, 8, 9, 12, 13}.  The four lane groups of a staged row pair would hit the same banks
+// (rows are 256 bytes): the 16-column block nj of a row staged by lane group g sits at position nj ^ g.
+constexpr bool S16 = kloop::Shape<kloop::Bf16>::S16;
+template <bool S> __device__ __forceinline__ constexpr int epi_pass_row(int it) { return S ? (it >> 1) * 16 + (it & 1) * 2 : it * 8; }
+template <bool S> __device__ __forceinline__ int epi_lane_row(int lane) {
+    const int j8 = lane >> 3;
+    return S ? 4 * (j8 >> 1) + (j8 & 1) : j8;
+}
+// where (in floats) lane l reads its chunk of a pass's 8 x 64 staging rows
+template <bool S> __device__ __forceinline__ int epi_read_off(int lane) {
+    const int j8 = lane >> 3, c8 = lane & 7;
+    return S ? j8 * 64 + (((c8 >> 1) ^ (j8 >> 1)) * 16 + (c8 & 1) * 8) : j8 * 64 + c8 * 8;
+}
+// 16x16x32: pass it of a 32-row block (its two accumulators; kloop.hpp for the quarters) -> the 8 x 64 floats at Cp
+__device__ __forceinline__ void stage_pass16(float* Cp, const f32x16 (&blk)[2], int it, int lane) {
+    const int g = lane >> 4, l15 = lane & 15;
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj)
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr)
+            Cp[(2 * g + rr) * 64 + ((nj ^ g) * 16 + l15)] = blk[nj >> 1][4 * (2 * (it >> 1) + (nj & 1)) + 2 * (it & 1) + rr];
+}
 constexpr int V4_SLAB = 64;                 // bytes of K per row per stage
 constexpr int V4_TILE = 128 * V4_SLAB;      // 8 KB per operand
 constexpr int V4_STAGE = 2 * V4_TILE;
@@ -521,22 +552,33 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel_v4(const GemmParams p) {
         }
     };
 
+    // bf16 on 16x16x32: 4 x 4 accumulators of f32x4, a slab is one k-step (kloop.hpp); fp32 and -DPV_GEMM_MFMA=32: 2 x 2 of f32x16
+    constexpr bool W16 = EB == 2 && S16;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+    kloop::zero(acc);
 
     const int l31 = lane & 31, half = lane >> 5;
-    const int sw = kloop::swz64(l31);
-    const int co0 = ((0 + half) ^ sw) * 16, co1 = ((2 + half) ^ sw) * 16;
-    const int a_row = (wm * 64 + l31) * V4_SLAB;
-    const int b_row = (wn * 64 + l31) * V4_SLAB;
+    const int frow = W16 ? (lane & 15) : l31;
+    const int sw = kloop::swz64(frow);
+    const int co0 = W16 ? ((lane >> 4) ^ sw) * 16 : ((0 + half) ^ sw) * 16, co1 = ((2 + half) ^ sw) * 16;
+    const int a_row = (wm * 64 + frow) * V4_SLAB;
+    const int b_row = (wn * 64 + frow) * V4_SLAB;
     auto compute = [&](const unsigned char* slot) {
         const unsigned char* Ab = slot;
         const unsigned char* Bb = slot + V4_TILE;
+        if constexpr (W16) {
+            uint4 a[4], b[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                a[i] = *reinterpret_cast<const uint4*>(Ab + a_row + i * 16 * V4_SLAB + co0);
+                b[i] = *reinterpret_cast<const uint4*>(Bb + b_row + i * 16 * V4_SLAB + co0);
+            }
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+                    kloop::mfma16_at(kloop::Bf16{}, acc[mi >> 1][ni >> 1], 2 * (mi & 1) + (ni & 1), a[mi], b[ni]);
+        } else {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int co = j == 0 ? co0 : co1;
@@ -564,6 +606,7 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel_v4(const GemmParams p) {
                             acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(
                                 __uint_as_float(au[mi][e]), __uint_as_float(bu[ni][e]), acc[mi][ni], 0, 0, 0);
             }
+        }
         }
     };
     // one pipeline step: slab kt lives in `cur`, slab kt+2 is issued into `nxt2` (the slot multiplied in step kt-1)
@@ -603,7 +646,7 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel_v4(const GemmParams p) {
                 for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                     for (int it = 0; it < 4; ++it) {
-                        const int gm = m0 + wm * 64 + mi * 32 + it * 8 + (lane >> 3);
+                        const int gm = m0 + wm * 64 + mi * 32 + epi_pass_row<W16>(it) + epi_lane_row<W16>(lane);
                         if (gm < p.M)
                             e_res[mi][it] = *reinterpret_cast<const uint4*>(
                                 reinterpret_cast<const T*>(p.resid) + (int64_t)gm * p.ldr + e_gn);
@@ -639,24 +682,29 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel_v4(const GemmParams p) {
     float* Cs = reinterpret_cast<float*>((wave < 2 ? ring0 : ring1) + (wave & 1) * (32 * CLD * 4));
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
+        if constexpr (W16) {
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
+            for (int it = 0; it < 4; ++it) stage_pass16(Cs + it * 8 * CLD, acc[mi], it, lane);
+        } else {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * half;
-                Cs[row * CLD + ni * 32 + l31] = acc[mi][ni][e];
-            }
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int row = (e & 3) + 8 * (e >> 2) + 4 * half;
+                    Cs[row * CLD + ni * 32 + l31] = acc[mi][ni][e];
+                }
+        }
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            const int row = it * 8 + (lane >> 3);
             const int cc = (lane & 7) * 8;
-            const int gm = m0 + wm * 64 + mi * 32 + row;
+            const int gm = m0 + wm * 64 + mi * 32 + epi_pass_row<W16>(it) + epi_lane_row<W16>(lane);
             const int gn = n0 + wn * 64 + cc;
             if (gm < p.M && gn < p.N) {
                 float v[8];
-                const float4 x0 = *reinterpret_cast<const float4*>(Cs + row * CLD + cc);
-                const float4 x1 = *reinterpret_cast<const float4*>(Cs + row * CLD + cc + 4);
+                const float* Cr = Cs + it * 8 * CLD + epi_read_off<W16>(lane);
+                const float4 x0 = *reinterpret_cast<const float4*>(Cr);
+                const float4 x1 = *reinterpret_cast<const float4*>(Cr + 4);
                 v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w;
                 v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
                 if constexpr (EB == 2) {
@@ -756,8 +804,8 @@ __device__ __forceinline__ void epi8_bf16(const float4& x0, const float4& x1, co
 template <typename T, int MB, int EPI, int ACT, int LP = 0>
 __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
     static_assert(sizeof(T) == 2, "v7 is the bf16 kernel");
-    using R64 = kloop::Ring64<MB>;
-    using R128 = kloop::Ring128<MB>;
+    using R64 = kloop::Ring64<MB, S16>;
+    using R128 = kloop::Ring128<MB, false, S16>;
     constexpr int TM = 64 * MB, TN = 256, SLOT = R64::SLOT, NA = R64::NA;
     static_assert(R128::SLOT == 2 * SLOT, "a full-line slot is two 64-byte-slab slots");
     // the ring slots, one object each (kloop.hpp).  LP >= 2 (full-line form): two slots of 128-byte rows in ring0 / ring1, the other
@@ -799,7 +847,8 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
     // The launcher guarantees vec_out and N % 8 == 0: whole 8-element chunks only.
     const int e_gn = n0 + wn * 64 + (lane & 7) * 8;
     const bool e_live = e_gn < p.N;
-    const int e_rows_left = e_live ? p.M - (m0 + wm * 32 * MB + (lane >> 3)) : 0;    // row mi*32 + it*8 of this lane is real iff < e_rows_left
+    const int e_lrow = epi_lane_row<S16>(lane);
+    const int e_rows_left = e_live ? p.M - (m0 + wm * 32 * MB + e_lrow) : 0;    // row mi*32 + pass_row(it) of this lane is real iff < e_rows_left
     uint4 e_bias = make_uint4(0, 0, 0, 0);
     constexpr int NRES = EPI == PV_EPI_RESID ? MB : 1;
     uint4 e_res[NRES][4];
@@ -809,12 +858,12 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
         for (int it = 0; it < 4; ++it) e_res[mi][it] = make_uint4(0, 0, 0, 0);
     int e_col = e_gn;
     T* e_out0 = reinterpret_cast<T*>(p.out0);
-    const T* e_rbase = reinterpret_cast<const T*>(p.resid) + (int64_t)(m0 + wm * 32 * MB + (lane >> 3)) * p.ldr + e_gn;
+    const T* e_rbase = reinterpret_cast<const T*>(p.resid) + (int64_t)(m0 + wm * 32 * MB + e_lrow) * p.ldr + e_gn;
 #define PV_V7_FETCH_RES(MI)                                                                          \
     if constexpr (EPI == PV_EPI_RESID) {                                                             \
         _Pragma("unroll") for (int it = 0; it < 4; ++it)                                             \
-            if ((MI) * 32 + it * 8 < e_rows_left)                                                    \
-                e_res[MI][it] = *reinterpret_cast<const uint4*>(e_rbase + (int64_t)((MI) * 32 + it * 8) * p.ldr); \
+            if ((MI) * 32 + epi_pass_row<S16>(it) < e_rows_left)                                     \
+                e_res[MI][it] = *reinterpret_cast<const uint4*>(e_rbase + (int64_t)((MI) * 32 + epi_pass_row<S16>(it)) * p.ldr); \
     }
     if (e_live) {
         const T* bias = reinterpret_cast<const T*>(p.bias0);
@@ -913,19 +962,24 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
     constexpr int CLD = 64;
     float* Cs = reinterpret_cast<float*>((wave < 4 ? ring0 : ring1) + (wave & 3) * (32 * CLD * 4));
     const pv_f32x2 e_b[4] = {unpack2(e_bias.x), unpack2(e_bias.y), unpack2(e_bias.z), unpack2(e_bias.w)};
-    const int64_t e_row0 = (int64_t)(m0 + wm * 32 * MB + (lane >> 3)) * p.ldo;
+    const int64_t e_row0 = (int64_t)(m0 + wm * 32 * MB + e_lrow) * p.ldo;
     T* const o0_base = e_out0 ? e_out0 + e_row0 + e_col : nullptr;
     T* const o1_base = reinterpret_cast<T*>(p.out1) + e_row0 + e_gn;
-    const float* Cr = Cs + (lane >> 3) * CLD + (lane & 7) * 8;
+    const float* Cr = Cs + epi_read_off<S16>(lane);
 #pragma unroll
     for (int mi = 0; mi < MB; ++mi) {
+        if constexpr (S16) {
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
+            for (int it = 0; it < 4; ++it) stage_pass16(Cs + it * 8 * CLD, acc[mi], it, lane);
+        } else {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * half;
-                Cs[row * CLD + ni * 32 + l31] = acc[mi][ni][e];
-            }
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int row = (e & 3) + 8 * (e >> 2) + 4 * half;
+                    Cs[row * CLD + ni * 32 + l31] = acc[mi][ni][e];
+                }
+        }
         __builtin_amdgcn_wave_barrier();
         // residual rows two blocks ahead: staging block mi freed 32 accumulator registers, which now carry the
         // rows of blocks 2mi+1 and 2mi+2 -- from block 2 on a load has two blocks of stores to land behind
@@ -934,10 +988,10 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
         if (2 * mi + 2 < MB) { PV_V7_FETCH_RES((2 * mi + 2 < MB ? 2 * mi + 2 : 0)) }
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            if (mi * 32 + it * 8 < e_rows_left) {
+            if (mi * 32 + epi_pass_row<S16>(it) < e_rows_left) {
                 const float4 x0 = *reinterpret_cast<const float4*>(Cr + it * 8 * CLD);
                 const float4 x1 = *reinterpret_cast<const float4*>(Cr + it * 8 * CLD + 4);
-                const int64_t ro = (int64_t)(mi * 32 + it * 8) * p.ldo;
+                const int64_t ro = (int64_t)(mi * 32 + epi_pass_row<S16>(it)) * p.ldo;
                 epi8_bf16<EPI, ACT>(x0, x1, e_b, o0_base ? o0_base + ro : nullptr, o1_base + ro,
                                     e_res[EPI == PV_EPI_RESID ? mi : 0][it]);
             }
@@ -975,7 +1029,7 @@ __device__ __forceinline__ int lane_id_here() {
 template <typename T, int MB, int EPI, int ACT>
 __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, const int ntiles, const int stagger) {
     static_assert(sizeof(T) == 2, "v8 is a bf16 kernel");
-    using R128 = kloop::Ring128<MB, true>;
+    using R128 = kloop::Ring128<MB, true, S16>;
     constexpr int TM = 64 * MB;
     constexpr int TN = 256;
     constexpr int A2 = R128::A_BYTES, B2 = R128::B_BYTES;             // one slot: (TM + TN) rows x 128 bytes of K
@@ -1027,8 +1081,12 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, con
     f32x16 acc[MB][2];
     kloop::zero(acc);
     // the tile's slabs alternate between the slots: even ones in ringA0 / ringB0
-#define PV_V8_EVEN(KT) kloop::step_full_line<kloop::Bf16>(acc, fa, fb, g, rsA, rsB, KT, ringA0, ringB0, ringA1, ringB1, src);
-#define PV_V8_ODD(KT) kloop::step_full_line<kloop::Bf16>(acc, fa, fb, g, rsA, rsB, KT, ringA1, ringB1, ringA0, ringB0, src);
+#define PV_V8_EVEN(KT)                                \
+    if constexpr (S16) kloop::keep_whole(acc);        \
+    kloop::step_full_line<kloop::Bf16>(acc, fa, fb, g, rsA, rsB, KT, ringA0, ringB0, ringA1, ringB1, src);
+#define PV_V8_ODD(KT)                                 \
+    if constexpr (S16) kloop::keep_whole(acc);        \
+    kloop::step_full_line<kloop::Bf16>(acc, fa, fb, g, rsA, rsB, KT, ringA1, ringB1, ringA0, ringB0, src);
 
     int vb = blockIdx.x;
     int m0, n0;
@@ -1064,7 +1122,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, con
         const int e_lane = lane_id_here();                                                                            \
         const int e_gn = n0 + wn * 64 + (e_lane & 7) * 8;                                                             \
         const bool e_live = e_gn < p.N;                                                                               \
-        const int e_rows_left = e_live ? p.M - (m0 + wm * 32 * MB + (e_lane >> 3)) : 0;                               \
+        const int e_rows_left = e_live ? p.M - (m0 + wm * 32 * MB + epi_lane_row<S16>(e_lane)) : 0;                   \
         int e_col = e_gn;                                                                                             \
         T* e_out0 = reinterpret_cast<T*>(p.out0);                                                                     \
         const T* e_biasp = reinterpret_cast<const T*>(p.bias0);                                                       \
@@ -1074,12 +1132,12 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, con
             if (which == 1) { e_out0 = reinterpret_cast<T*>(p.out1); e_biasp = reinterpret_cast<const T*>(p.bias1); } \
             if (which == 2) { e_out0 = reinterpret_cast<T*>(p.out2); e_biasp = reinterpret_cast<const T*>(p.bias2); } \
         }                                                                                                             \
-        const T* e_rbase = reinterpret_cast<const T*>(p.resid) + (int64_t)(m0 + wm * 32 * MB + (e_lane >> 3)) * p.ldr + e_gn;
+        const T* e_rbase = reinterpret_cast<const T*>(p.resid) + (int64_t)(m0 + wm * 32 * MB + epi_lane_row<S16>(e_lane)) * p.ldr + e_gn;
 #define PV_V8_FETCH_RES(MI)                                                                          \
         if constexpr (EPI == PV_EPI_RESID) {                                                         \
             _Pragma("unroll") for (int it = 0; it < 4; ++it)                                         \
-                if ((MI) * 32 + it * 8 < e_rows_left)                                                \
-                    e_res[MI][it] = *reinterpret_cast<const uint4*>(e_rbase + (int64_t)((MI) * 32 + it * 8) * p.ldr); \
+                if ((MI) * 32 + epi_pass_row<S16>(it) < e_rows_left)                                 \
+                    e_res[MI][it] = *reinterpret_cast<const uint4*>(e_rbase + (int64_t)((MI) * 32 + epi_pass_row<S16>(it)) * p.ldr); \
         }
         // k-step 0's fragments of the tile's first slab (visible since the last barrier of the previous tile's loop; that loop's
         // last refills fetched the same values, but carrying 36 registers across the epilogue costs the loop body spills)
@@ -1107,32 +1165,36 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v8(const GemmParams p, con
         PV_V8_EPI_GEOMETRY()
         (void)e_biasp;
         const pv_f32x2 e_b[4] = {unpack2(e_bias.x), unpack2(e_bias.y), unpack2(e_bias.z), unpack2(e_bias.w)};
-        const int64_t e_row0 = (int64_t)(m0 + wm * 32 * MB + (e_lane >> 3)) * p.ldo;
+        const int64_t e_row0 = (int64_t)(m0 + wm * 32 * MB + epi_lane_row<S16>(e_lane)) * p.ldo;
         T* const o0_base = e_out0 ? e_out0 + e_row0 + e_col : nullptr;
         T* const o1_base = reinterpret_cast<T*>(p.out1) + e_row0 + e_gn;
         float* const Cs = reinterpret_cast<float*>(stage + wave * 2048);
-        const float* const Cr = Cs + (e_lane >> 3) * 64 + (e_lane & 7) * 8;
-        float* const Cw = Cs + (e_lane >> 5) * 256 + (e_lane & 31);
+        const float* const Cr = Cs + epi_read_off<S16>(e_lane);
+        [[maybe_unused]] float* const Cw = Cs + (e_lane >> 5) * 256 + (e_lane & 31);
         if constexpr (MB >= 5) { PV_V8_FETCH_RES(0) }
 #pragma unroll
         for (int mi = 0; mi < MB; ++mi) {
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
+                if constexpr (S16) {
+                    stage_pass16(Cs, acc[mi], it, e_lane);
+                } else {
 #pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
+                    for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        Cw[j * 64 + ni * 32] = acc[mi][ni][4 * it + j];
+                        for (int j = 0; j < 4; ++j)
+                            Cw[j * 64 + ni * 32] = acc[mi][ni][4 * it + j];
+                }
                 __builtin_amdgcn_wave_barrier();
                 if (it == 0) {
                     // residual rows two blocks ahead, as v7
                     if (2 * mi + 1 < MB) { PV_V8_FETCH_RES((2 * mi + 1 < MB ? 2 * mi + 1 : 0)) }
                     if (2 * mi + 2 < MB) { PV_V8_FETCH_RES((2 * mi + 2 < MB ? 2 * mi + 2 : 0)) }
                 }
-                if (mi * 32 + it * 8 < e_rows_left) {
+                if (mi * 32 + epi_pass_row<S16>(it) < e_rows_left) {
                     const float4 x0 = *reinterpret_cast<const float4*>(Cr);
                     const float4 x1 = *reinterpret_cast<const float4*>(Cr + 4);
-                    const int64_t ro = (int64_t)(mi * 32 + it * 8) * p.ldo;
+                    const int64_t ro = (int64_t)(mi * 32 + epi_pass_row<S16>(it)) * p.ldo;
                     epi8_bf16<EPI, ACT>(x0, x1, e_b, o0_base ? o0_base + ro : nullptr, o1_base + ro,
                                         e_res[EPI == PV_EPI_RESID ? mi : 0][it]);
                 }
