@@ -19,6 +19,7 @@ from oracle.vit_oracle import fingerprint, hook_names_in_order, vit_forward
 from vit_prisma_amd import ActivationCache, HookedViT, HookedViTConfig, _native
 from vit_prisma_amd.synth import ARCHS, synth_images, synth_vit_state
 
+from _attention_cases import pattern_elementwise_ok
 from conftest import GOLDEN, rel_fro
 
 pytestmark = pytest.mark.gpu
@@ -358,6 +359,8 @@ def test_bf16_attention_core_against_fp32_recompute_of_its_own_inputs(arch_name,
         p_ref = torch.softmax(s_got, dim=-1)
         p_got = cache[pre + "hook_pattern"].float()
         assert float((p_got - p_ref).abs().max()) <= 2 ** -8, layer
+        # per element, relative: 2^-8 p + 1e-30 (tests/_attention_cases.py) -- the absolute bound alone passes an all-zero pattern at T = 577
+        assert pattern_elementwise_ok(p_got, p_ref)[0], (layer, pattern_elementwise_ok(p_got, p_ref)[1])
         assert torch.allclose(p_got.sum(-1), torch.ones_like(p_got.sum(-1)), atol=2e-2)
         z_ref = torch.einsum("bhqk,bkhd->bqhd", p_got, v)
         z_got = cache[pre + "hook_z"].float()
@@ -999,12 +1002,15 @@ def test_bf16_long_sequence_attention_kernel(image_size, patch):
     assert float((s_got - s_ref).abs().max()) <= 2 ** -8 * float(s_ref.abs().max()) + 1e-6
     p_got = cache["blocks.0.attn.hook_pattern"].float()
     assert float((p_got - torch.softmax(s_got, dim=-1)).abs().max()) <= 2 ** -8
+    # per element, relative: 2^-8 p + 1e-30 (tests/_attention_cases.py) -- every element here is below the absolute bound
+    assert pattern_elementwise_ok(p_got, torch.softmax(s_got, dim=-1))[0], pattern_elementwise_ok(p_got, torch.softmax(s_got, dim=-1))[1]
     z_ref = torch.einsum("bhqk,bkhd->bqhd", p_got, v)
     z_got = cache["blocks.0.attn.hook_z"].float()
     assert float((z_got - z_ref).abs().max()) <= 2 ** -8 * float(z_ref.abs().max()) + 1e-6
     # without the score tap: the same statements against the same fp32 recompute, and the same z whichever taps are taken
     p2 = pat_z["blocks.0.attn.hook_pattern"].float()
     assert p2.shape == (3, 2, T, T) and float((p2 - torch.softmax(s_got, dim=-1)).abs().max()) <= 2 ** -8
+    assert pattern_elementwise_ok(p2, torch.softmax(s_got, dim=-1))[0]
     z2 = pat_z["blocks.0.attn.hook_z"].float()
     assert float((z2 - torch.einsum("bhqk,bkhd->bqhd", p2, v)).abs().max()) <= 2 ** -8 * float(z_ref.abs().max()) + 1e-6
     assert torch.equal(only_z["blocks.0.attn.hook_z"], pat_z["blocks.0.attn.hook_z"])
