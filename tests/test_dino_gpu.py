@@ -16,6 +16,7 @@ import torch
 from vit_prisma_amd import HookedViT, HookedViTConfig
 from vit_prisma_amd.synth import synth_images
 
+import _rowop_cases as RC
 from _attention_cases import pattern_elementwise_ok
 from test_dino_cpu import GOLDEN, POOLED_ARCHS, POOLED_BATCH, POOLED_KEYS, pooled_model, rel_fro
 
@@ -186,6 +187,13 @@ def check_pooled_vector(model, x, tag, dtype):
         close(pooled[..., 1], lnf[:, 1:].mean(dim=1), dtype, "mean over the patch tokens")
         want_out = torch.nn.functional.normalize(pooled.float(), dim=-1)
     close(out, want_out, dtype, "normalised output")
+    # per column / per element (tests/_rowop_cases.py): the float64 mean of the cached hook_ln_final, the float64 normalise of the pooled vector
+    bf16 = dtype == torch.bfloat16
+    t0 = 0 if tag == "gaap" else 1
+    r_mean = RC.check_token_mean(cache["hook_ln_final"].cpu(), (pooled if tag == "gaap" else pooled[..., 1]).cpu(), t0, bf16)
+    r_norm = RC.check_l2norm(pooled.cpu().reshape(-1, pooled.shape[-1]), out.cpu().reshape(-1, pooled.shape[-1]), bf16)
+    print(f"{tag} d_model {d} T {T}: error / bound  token mean {r_mean:.3g}  l2 normalise {r_norm:.3g}")
+    assert r_mean <= 1.0 and r_norm <= 1.0, (tag, d, T, r_mean, r_norm)
 
 
 @pytest.mark.parametrize("tag", sorted(POOLED_ARCHS))
@@ -202,6 +210,79 @@ def test_dino_vitb_pooling_meets_long_attention_at_785(dtype):
     assert model.n_tokens == 785
     x = torch.randn(2, 3, 112, 112, device="cuda", generator=torch.Generator(device="cuda").manual_seed(7)).to(dtype)
     check_pooled_vector(model, x, "dino", dtype)
+
+
+def wide_pooled_model(tag, dtype, d_model, image_size, cls, n_layers):
+    """a head-less pooled model at a d_model beyond one 128-column workgroup of token_mean_kernel (patch 4)"""
+    cfg = dict(n_layers=n_layers, d_model=d_model, n_heads=2, d_head=32, d_mlp=64, patch_size=4, image_size=image_size, n_channels=3,
+               n_classes=16, eps=1e-5, layer_norm_pre=True, normalize_output=True, return_type="pre_logits", activation_name="gelu",
+               use_cls_token=cls, normalization_type="LN", classification_type="gaap" if tag == "gaap" else "cls",
+               model_name="synthetic-wide-gaap" if tag == "gaap" else "facebook/dino-vitb-wide")
+    torch.manual_seed(d_model + image_size)
+    model = HookedViT(HookedViTConfig(**cfg, dtype=dtype, device="cuda")).to(dtype).cuda().eval().use_native(True)
+    with torch.no_grad():                                 # (an ln_final away from the identity, so that the columns differ in size)
+        model.ln_final.w.copy_(RC.ln_weights(d_model)[0].to(dtype))
+        model.ln_final.b.copy_(RC.ln_weights(d_model)[1].to(dtype))
+    x = torch.randn(POOLED_BATCH, 3, image_size, image_size, device="cuda",
+                    generator=torch.Generator(device="cuda").manual_seed(d_model)).to(dtype)
+    return model, x
+
+
+# token_mean_kernel: a workgroup owns 128 columns (a lane two), wave w the tokens t0 + w, t0 + w + 4, ...
+#   d_model 136   two workgroups in x, the second with 4 active lanes          d_model 264   three, the last with 4 active lanes
+#   T = 17        every wave has tokens                                        T - t0 = 1, 2  three / two waves have none: "gaap" without
+#   a cls token at one patch (T = 1), with it (T = 2); the dino concatenation at one patch (T = 2, t0 = 1).  T - t0 = 3 does not exist
+#   on a square patch grid.  The few-token models have no blocks (n_layers = 0): ln_final reads the embedding stage's output.
+WIDE = [(tag, d, 16, True, 1) for tag in ("gaap", "dino") for d in (136, 264)] + \
+       [("gaap", 264, 4, False, 0), ("gaap", 136, 4, True, 0), ("dino", 264, 4, True, 0)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("tag,d_model,image_size,cls,n_layers", WIDE,
+                         ids=[f"{w[0]}-d{w[1]}-T{(w[2] // 4) ** 2 + int(w[3])}" for w in WIDE])
+def test_pooled_vector_beyond_one_workgroup_and_with_idle_waves(tag, d_model, image_size, cls, n_layers, dtype):
+    model, x = wide_pooled_model(tag, dtype, d_model, image_size, cls, n_layers)
+    assert model.n_tokens == (image_size // 4) ** 2 + int(cls)
+    check_pooled_vector(model, x, tag, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("batch", [1, 5])
+@pytest.mark.parametrize("n_classes", [16, 136, 1000])
+def test_l2_normalise_per_row_ragged_workgroup_and_a_zero_row(n_classes, batch, dtype):
+    """l2norm_kernel on the head's output: rows = B in {1, 5} (a 4-row workgroup with 1 row; one full and one with 1), row lengths 16
+    (a quarter of the lanes), 136 and 1000 (no multiple of 64), every element against float64 x / max(||x||, 1e-12).  At B = 5 image 2
+    is handed a constant CLS row by a hook on the last hook_resid_post: with ln_final.b = 0 its LayerNorm is exactly 0, the head (b_H =
+    0) gives an all-zero row, and that row must stay zero."""
+    cfg = dict(n_layers=1, d_model=64, n_heads=2, d_head=32, d_mlp=64, patch_size=4, image_size=8, n_channels=3, n_classes=n_classes,
+               eps=1e-5, layer_norm_pre=True, normalize_output=True, return_type="class_logits", activation_name="gelu",
+               use_cls_token=True, normalization_type="LN", classification_type="cls")
+    torch.manual_seed(n_classes)
+    model = HookedViT(HookedViTConfig(**cfg, dtype=dtype, device="cuda")).to(dtype).cuda().eval().use_native(True)
+    with torch.no_grad():
+        model.ln_final.b.zero_()
+        model.head.b_H.zero_()
+    x = torch.randn(batch, 3, 8, 8, device="cuda", generator=torch.Generator(device="cuda").manual_seed(batch)).to(dtype)
+    zero_row = 2 if batch == 5 else None
+
+    def flatten_cls(t, hook=None):
+        t = t.clone()
+        if zero_row is not None:
+            t[zero_row, 0, :] = 1.5
+        return t
+
+    with torch.no_grad():
+        out, cache = model.run_with_cache(x, fwd_hooks=[("blocks.0.hook_resid_post", flatten_cls)])
+    assert model.last_run_native, model.native_fallback_reason
+    head = cache["hook_post_head_pre_normalize"]
+    assert head.shape == out.shape == (batch, n_classes) and out.dtype == dtype
+    if zero_row is not None:
+        assert float(head[zero_row].abs().max()) == 0.0 and float(out[zero_row].abs().max()) == 0.0
+        assert float(head[[0, 1, 3, 4]].float().abs().amax(-1).min()) > 0.0
+    r = RC.check_l2norm(head.cpu(), out.cpu(), dtype == torch.bfloat16)
+    print(f"l2 normalise {n_classes} x {batch}: error / bound {r:.3g} ({RC.l2norm_units(n_classes):.1f} u)")
+    assert r <= 1.0, r
+    close(out, torch.nn.functional.normalize(head.float(), dim=-1), dtype, "normalised output")
 
 
 def test_hook_on_ln_final_of_dino_vitb_gives_the_pytorch_answer():

@@ -144,7 +144,8 @@ __device__ __forceinline__ pv_f32x2 act2(pv_f32x2 x) {
         const pv_f32x2 hx = x * 0.5f;
         return __builtin_elementwise_fma(hx, r, hx);
     } else {
-        return __builtin_elementwise_max(x, pv_f32x2{0.0f, 0.0f});
+        // F.relu keeps a NaN; v_max_f32 / v_pk_max_f32 (maxnum) would return the 0 beside it.  A compare that NaN fails selects x.
+        return pv_f32x2{x.x < 0.0f ? 0.0f : x.x, x.y < 0.0f ? 0.0f : x.y};
     }
 }
 

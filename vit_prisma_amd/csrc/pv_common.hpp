@@ -211,7 +211,7 @@ __device__ __forceinline__ float pv_act(float x, int act) {
         else return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
     }
     if (act == PV_ACT_QUICK_GELU) return x / (1.0f + __expf(-1.702f * x));
-    return fmaxf(x, 0.0f);
+    return x < 0.0f ? 0.0f : x;   // (not fmaxf: F.relu keeps a NaN, maxnum returns the 0 beside it)
 }
 
 // ---------------------------------------------------------------------------------------------
