@@ -46,8 +46,9 @@ extern "C" {
  * 11: pv_sae_tp_merge / pv_sae_tp_bucket_*, pv_build_id, the dense ReLU + L1 step pv_sae_dense_*; 17: pv_gemm_epilogue, the
  * gemm_persist / gemm_stagger tuning keys; 22: pv_sae_desc.activation / lp_norm,
  * normalize_layer_norm = 2 (constant_norm_rescale), the split-fp16 dense GEMMs and their tuning key dense_fp32, gemm_cus;
- * 24: pv_vit_desc.pooling, PV_ATTN_MAX_TOKENS = 2048 (was 640)). */
-#define PV_ABI_VERSION 24
+ * 24: pv_vit_desc.pooling, PV_ATTN_MAX_TOKENS = 2048 (was 640);
+ * 25: the supported attention shapes gain the wide heads, 64 < d_head <= 128 with d_head % 8 == 0 (CLIP ViT-H / g / bigG-14)). */
+#define PV_ABI_VERSION 25
 int pv_abi_version(void);
 /* Hash of the sources this binary was built from (sha256 over the .hip / .hpp files of vit_prisma_amd/csrc and this header, names and
  * contents, sorted; first 32 hex digits): the prebuilt library travels next to the sources, and the Python binding refuses
@@ -61,7 +62,7 @@ void pv_last_error(char* buf, size_t len);
 /* of prisma_tools/hooked_root_module.py:289-332 fused in as tap stores)                        */
 /* ------------------------------------------------------------------------------------------ */
 
-/* Largest n_tokens the attention kernels serve (d_head 32 or 64): THE cap -- pv_vit_plan_create, the attention launchers and the
+/* Largest n_tokens the attention kernels serve (d_head 32 or 64, or 64 < d_head <= 128 with d_head % 8 == 0): THE cap -- pv_vit_plan_create, the attention launchers and the
  * Python binding (_native.ATTN_MAX_TOKENS, NativeViT.supported) all state and enforce this number.  2048 covers 224 px / 8 (785),
  * 448 px / 16 (785) and 448 - 518 px / 14 (1025 - 1370) with room to spare; it is a stated cap, not a hardware limit. */
 #define PV_ATTN_MAX_TOKENS 2048

@@ -11,9 +11,15 @@ from typing import Optional
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PV_NATIVE_LIB") or os.path.join(HERE, "libpvnative.so")     # (override: kernel A/B builds)
-ABI_VERSION = 24
+ABI_VERSION = 25
 ATTN_MAX_TOKENS = 2048            # PV_ATTN_MAX_TOKENS of include/pv_native.h (held equal by tests/test_dino_cpu.py)
 PV_POOL_CLS, PV_POOL_MEAN, PV_POOL_CLS_MEAN = 0, 1, 2
+
+
+def attention_head_supported(d_head: int) -> bool:
+    """The d_head rule of pv_attention_supported (csrc/attention.hip): 32, 64, or a wide head 64 < d_head <= 128, d_head % 8 == 0."""
+    return d_head in (32, 64) or (64 < d_head <= 128 and d_head % 8 == 0)
+
 
 PV_DTYPE_F32, PV_DTYPE_BF16 = 0, 1
 PV_ACT = {"gelu": 0, "quick_gelu": 1, "relu": 2}

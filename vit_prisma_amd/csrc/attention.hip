@@ -1325,7 +1325,8 @@ int dispatch_attn(AttnParams& p, hipStream_t stream) {
         if (p.dh == 64) return launch_attn_stream<T, 64>(p, stream);
         if (p.dh == 32) return launch_attn_stream<T, 32>(p, stream);
     }
-    pv_set_error("attention: unsupported (T, d_head); supported: T <= " PV_STR(PV_ATTN_MAX_TOKENS) ", d_head in {32, 64}");
+    pv_set_error("attention: unsupported (T, d_head); supported: T <= " PV_STR(PV_ATTN_MAX_TOKENS)
+                 ", d_head in {32, 64} or 64 < d_head <= 128 with d_head % 8 == 0");
     return PV_ERR_INVALID;
 }
 
@@ -1376,24 +1377,28 @@ __global__ __launch_bounds__(256) void attn_resume_kernel(const AttnParams p, in
         for (int c = lane; c < T_; c += 64) pr[c] = DT<T>::load(in + c);
     }
     __builtin_amdgcn_wave_barrier();
-    // z[t, h, :] = sum_c pattern[c] v[c, h, :]  (attention.py:267-281); lane = d (two passes for d_head > 64 never occur: dh <= 64)
+    // z[t, h, :] = sum_c pattern[c] v[c, h, :]  (attention.py:267-281); lane = d, a second round for the wide heads (64 < d_head <= 128)
     const T* vb = reinterpret_cast<const T*>(p.v) + ((int64_t)b * T_ * H + h) * dh;
     const int64_t tok = (int64_t)H * dh;
-    if (lane < dh) {
+    for (int d = lane; d < dh; d += 64) {
         float acc = 0.f;
-        for (int c = 0; c < T_; ++c) acc = fmaf(pr[c], DT<T>::load(vb + c * tok + lane), acc);
-        DT<T>::store(reinterpret_cast<T*>(p.z) + ((int64_t)b * T_ * H + h) * dh + (int64_t)t * tok + lane, acc);
+        for (int c = 0; c < T_; ++c) acc = fmaf(pr[c], DT<T>::load(vb + c * tok + d), acc);
+        DT<T>::store(reinterpret_cast<T*>(p.z) + ((int64_t)b * T_ * H + h) * dh + (int64_t)t * tok + d, acc);
     }
 }
 
 }  // namespace
 
-int pv_attention_supported(int T, int dh) { return (T <= PV_ATTN_MAX_TOKENS && (dh == 64 || dh == 32)) ? 1 : 0; }
+int pv_attention_supported(int T, int dh) {
+    return (T <= PV_ATTN_MAX_TOKENS && (dh == 64 || dh == 32 || pv_attention_wide_supported(dh))) ? 1 : 0;
+}
 
 int pv_launch_attention(int dtype, AttnParams p, hipStream_t stream) {
     PV_REQUIRE(p.q && p.k && p.v && p.z, "attention operands must be non-null");
     PV_REQUIRE(pv_aligned16(p.q) && pv_aligned16(p.k) && pv_aligned16(p.v), "attention operands must be 16-byte aligned");
     PV_REQUIRE(p.B <= 65535 && p.H <= 65535, "attention grid limits");
+    // wide heads (64 < d_head <= 128): attn_wide_kernel (attention_wide.hip) at every T, before the table of d_head 32 / 64
+    if (p.dh > 64) return pv_launch_attention_wide(dtype, p, stream);
     if (dtype == PV_DTYPE_BF16) return dispatch_attn<bf16_t>(p, stream);
     if (dtype == PV_DTYPE_F32) return dispatch_attn<float>(p, stream);
     pv_set_error("attention: unsupported dtype");
@@ -1402,7 +1407,7 @@ int pv_launch_attention(int dtype, AttnParams p, hipStream_t stream) {
 
 int pv_launch_attention_resume(int dtype, AttnParams p, int from_scores, hipStream_t stream) {
     PV_REQUIRE(p.v && p.z && (from_scores ? p.scores != nullptr : p.pattern != nullptr), "attention resume operands must be non-null");
-    PV_REQUIRE(p.T >= 1 && p.T <= PV_ATTN_MAX_TOKENS && p.dh >= 1 && p.dh <= 64, "attention resume: T <= " PV_STR(PV_ATTN_MAX_TOKENS) ", d_head <= 64");
+    PV_REQUIRE(p.T >= 1 && p.T <= PV_ATTN_MAX_TOKENS && p.dh >= 1 && p.dh <= 128, "attention resume: T <= " PV_STR(PV_ATTN_MAX_TOKENS) ", d_head <= 128");
     const int64_t rows = (int64_t)p.B * p.H * p.T;
     PV_REQUIRE((rows + 3) / 4 < (1ll << 31), "attention resume grid");
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);

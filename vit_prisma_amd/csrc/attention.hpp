@@ -13,6 +13,9 @@ struct AttnParams {
 
 int pv_attention_supported(int T, int dh);
 int pv_launch_attention(int dtype, AttnParams p, hipStream_t stream);
+// Wide heads, 64 < d_head <= 128 with d_head % 8 == 0 (attention_wide.hip): pv_launch_attention sends them here at every T.
+int pv_attention_wide_supported(int dh);
+int pv_launch_attention_wide(int dtype, const AttnParams& p, hipStream_t stream);
 // The attention core resumed behind a hooked activation (pv_vit_forward_stage, PV_STAGE_SCORES / PV_STAGE_PATTERN):
 // from_scores: p.scores is the INPUT (the edited hook_attn_scores tensor): pattern = softmax, NaN -> 0 (attention.py:148-150),
 // written to p.pattern when non-NULL, z = pattern v; otherwise p.pattern is the INPUT (the edited hook_pattern tensor) and

@@ -56,7 +56,7 @@ extern "C" int pv_vit_plan_create(const pv_vit_desc* desc, pv_vit_plan** out_pla
     const int G = d.image_size / d.patch_size;
     const int P = G * G;
     PV_REQUIRE(d.n_tokens == P + (d.use_cls_token ? 1 : 0), "n_tokens != patches (+cls)");
-    PV_REQUIRE(pv_attention_supported(d.n_tokens, d.d_head), "attention shape unsupported (T <= " PV_STR(PV_ATTN_MAX_TOKENS) ", d_head in {32,64})");
+    PV_REQUIRE(pv_attention_supported(d.n_tokens, d.d_head), "attention shape unsupported (T <= " PV_STR(PV_ATTN_MAX_TOKENS) ", d_head in {32, 64} or 64 < d_head <= 128 with d_head % 8 == 0)");
     PV_REQUIRE(d.pooling >= PV_POOL_CLS && d.pooling <= PV_POOL_CLS_MEAN, "pooling");
     // cat(cls, mean(patches)) is [B, d_model, 2]: the reference's registry has it without a head only (base_vit.py:199-208)
     PV_REQUIRE(d.pooling != PV_POOL_CLS_MEAN || (!d.has_head && d.n_tokens >= 2), "PV_POOL_CLS_MEAN needs has_head == 0 and a patch token");

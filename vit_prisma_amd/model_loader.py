@@ -3,7 +3,7 @@
 
 The reference resolves ``model_name`` to a config and to weights by downloading from HuggingFace (model_loader.py:397-407, 775-784);
 there is no network here.  This loader therefore takes the config from the architecture tables of ``synth.ARCHS`` plus the
-per-name overrides of the reference registry (``NAME_OVERRIDES``) -- what ``load_config`` would have produced for these names, SURVEY.md 8a -- and the weights from a LOCAL open_clip / HuggingFace CLIP checkpoint, or for the DINO names (``DINO_ARCH``) a HuggingFace ``ViTModel`` one
+per-name overrides of the reference registry (``NAME_OVERRIDES``) -- what ``load_config`` would have produced for these names, SURVEY.md 8a -- and the weights from a LOCAL open_clip / HuggingFace CLIP checkpoint, or for the DINO names (``DINO_ARCH``) a HuggingFace ``ViTModel`` one; the wide-head open_clip towers H/14, g/14 and bigG/14 are ``WIDE_ARCH``
 (``local_path=...``: a ``.safetensors`` / ``.pt`` / ``.bin`` file, converted by ``weights.py`` exactly as the reference's converters do) --
 or none (``pretrained=False``: the reference's initialisation).  Everything else about the signature is the reference's; the options
 that rewrite weights (``fold_ln``, ``center_writing_weights``, ``refactor_factored_attn_matrices``) are not implemented and raise
@@ -47,18 +47,25 @@ DINO_ARCH = {
     "facebook/dino-vits16": "dino-vits16",
     "facebook/dino-vits8": "dino-vits8",
 }
+# the wide-head open_clip towers (registry :253-258, :326-328 over BASE_OPEN_CLIP_CONFIGS :58-78): heads of 80, 88 and 104, open_clip
+# checkpoints like the B/32 names.  Pinned by tests/golden/model_registry_wide.json (tests/golden/gen_golden_vit_wide.py).
+WIDE_ARCH = {
+    "open-clip:laion/CLIP-ViT-H-14-laion2B-s32B-b79K": "clip-vit-h14",
+    "open-clip:laion/CLIP-ViT-g-14-laion2B-s34B-b88K": "clip-vit-g14",
+    "open-clip:laion/CLIP-ViT-bigG-14-laion2B-39B-b160k": "clip-vit-bigg14",
+}
 DTYPE_FROM_STRING = {"float32": torch.float32, "fp32": torch.float32, "float16": torch.float16, "fp16": torch.float16,
                      "bfloat16": torch.bfloat16, "bf16": torch.bfloat16}
 
 
 def list_available_models():
-    return sorted({**MODEL_ARCH, **DINO_ARCH})
+    return sorted({**MODEL_ARCH, **DINO_ARCH, **WIDE_ARCH})
 
 
 def load_config(model_name: str, dtype: torch.dtype = torch.float32, device: str = "cuda", **overrides) -> HookedViTConfig:
-    if model_name not in MODEL_ARCH and model_name not in DINO_ARCH:
+    if model_name not in MODEL_ARCH and model_name not in DINO_ARCH and model_name not in WIDE_ARCH:
         raise ValueError(f"{model_name!r}: offline build knows {list_available_models()} (no network: configs cannot be downloaded)")
-    kw = dict(ARCHS[MODEL_ARCH.get(model_name) or DINO_ARCH[model_name]])
+    kw = dict(ARCHS[MODEL_ARCH.get(model_name) or DINO_ARCH.get(model_name) or WIDE_ARCH[model_name]])
     kw["model_name"] = model_name
     kw.update(NAME_OVERRIDES.get(model_name, {}))
     kw.update(overrides)

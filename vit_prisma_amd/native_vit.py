@@ -166,7 +166,7 @@ class NativeViT:
             return "architecture variant"
         if cfg.d_model % 8 or cfg.d_mlp % 8 or cfg.d_model > 2048:
             return "d_model/d_mlp alignment"
-        if n_tokens > N.ATTN_MAX_TOKENS or cfg.d_head not in (32, 64):
+        if n_tokens > N.ATTN_MAX_TOKENS or not N.attention_head_supported(cfg.d_head):
             return "attention shape"
         if pooling_mode(cfg) == N.PV_POOL_CLS_MEAN and n_tokens < 2:
             return "classification_type: no patch token to average"
