@@ -367,7 +367,7 @@ __device__ __forceinline__ void st4_stream(float* p, const float4& v) {
 // total (offs[d_sae], scalars[2] = l0) and the zeroing of the long-list counters.  The loss reduction that rides in csr_scan_kernel's
 // workgroup cannot come along (it needs the decode kernel's output): loss_reduce_body, a role of csr_post_fill_kernel.
 struct ScanRole {
-    const uint32_t* cnt; uint32_t* offs; uint32_t* n_long; int d_sae; float* scalars; float inv_tokens;
+    const uint32_t* cnt; uint32_t* offs; uint32_t* n_long; int d_sae; float* scalars; float tokens;
 };
 __device__ __forceinline__ void scan_body_256(const ScanRole& r) {
     __shared__ uint32_t sc_wsum[4];
@@ -420,7 +420,8 @@ __device__ __forceinline__ void scan_body_256(const ScanRole& r) {
     }
     if (tid == 255) {
         r.offs[r.d_sae] = total;
-        if (r.scalars) r.scalars[2] = (float)total * r.inv_tokens;      // l0 = mean_n #(val > 0), train_sae.py:364
+        if (r.scalars) r.scalars[2] = (float)total / r.tokens;          // l0 = mean_n #(val > 0), train_sae.py:364 (a division: total * (1 / N)
+                                                                        // is an ulp off at some N -- 1328 pairs of 166 tokens gave 7.9999995)
     }
     if (tid == 0) { r.n_long[0] = 0u; r.n_long[1] = 0u; r.n_long[2] = 0u; }      // counters of csr_post_kernel; the ticket of colsum_final_sq_kernel
 }
@@ -487,7 +488,9 @@ __global__ __launch_bounds__(256) void sae_decode_kernel(
         for (int u = 0; u < DEC_R; ++u) {
             const int su = min(s + u, k - 1);
             const int ju = ir[su];
-            a[u] = s + u < k_walk ? vr[su] : 0.f;
+            const float v = s + u < k_walk ? vr[su] : 0.f;
+            a[u] = v > 0.f ? v : 0.f;                             // a value <= 0 is a hole (pv_native.h): a negative one the caller of
+                                                                  // pv_sae_tp_partial / pv_sae_tp_finish hands over adds nothing either
             const bool live = a[u] != 0.f;                        // (wave-uniform) a hole -- a candidate that lost the global top-k of the
                                                                   // feature-parallel step, a clamped negative -- gathers nothing
             if (inv_norm) a[u] *= inv_norm[ju];
@@ -637,7 +640,7 @@ static inline bool sae_long_ranged(int n_tokens) { return (size_t)n_tokens * 4 +
 // their sum in a fixed order (the step's loss; it used to be a launch of its own in front of this one)
 __global__ __launch_bounds__(1024) void csr_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ offs,
                                                         uint32_t* __restrict__ n_long, int d_sae,
-                                                        float* __restrict__ scalars, float inv_tokens,
+                                                        float* __restrict__ scalars, float tokens,
                                                         const float* __restrict__ loss_part = nullptr, int n_loss = 0,
                                                         float loss_scale = 0.f) {
     constexpr int BLK = 32768;
@@ -692,7 +695,7 @@ __global__ __launch_bounds__(1024) void csr_scan_kernel(const uint32_t* __restri
     }
     if (tid == 1023) {
         offs[d_sae] = carry;
-        if (scalars) scalars[2] = (float)carry * inv_tokens;            // l0 = mean_n #(val > 0), train_sae.py:364
+        if (scalars) scalars[2] = (float)carry / tokens;                // l0 = mean_n #(val > 0), train_sae.py:364 (divided, as in scan_body_256)
     }
     if (tid == 0) { n_long[0] = 0u; n_long[1] = 0u; n_long[2] = 0u; }   // counters of csr_post_kernel; the ticket of colsum_final_sq_kernel
 }
@@ -2180,7 +2183,7 @@ static int sae_csr_build(pv_sae_plan* plan, pv_sae_state* st, int N, int k, cons
         // :620-626 -- scalars[0] = scalars[1])
         if (!folded)
             hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(1024), 0, stream, cnt, offs, n_long, d.d_sae,
-                               scalars, 1.0f / (float)N, loss_part, loss_part ? N : 0, loss_scale);
+                               scalars, (float)N, loss_part, loss_part ? N : 0, loss_scale);
         // chunk cuts / long lists / statistics, the scatter of the pairs and (autoencoder) the partial column sums of dY: one launch
         {
             CsrPostArgs pa;
@@ -2302,7 +2305,7 @@ int sae_sparse_tail(pv_sae_plan* plan, pv_sae_state* st, const float* x, int N, 
         ScanRole scan = {};
         if (folded) {
             scan.cnt = (const uint32_t*)(wsb + ws.cnt); scan.offs = (uint32_t*)(wsb + ws.offs); scan.n_long = (uint32_t*)(wsb + ws.n_long);
-            scan.d_sae = d.d_sae; scan.scalars = scalars; scan.inv_tokens = 1.0f / (float)N;
+            scan.d_sae = d.d_sae; scan.scalars = scalars; scan.tokens = (float)N;
         }
         const dim3 grid_dec((N + 3) / 4 + (folded ? 1 : 0));
 #define CALL(D)                                                                                                      \
@@ -3085,7 +3088,7 @@ extern "C" int pv_sae_tp_finish(pv_sae_plan* plan, pv_sae_state* st, const float
         const float grad_scale = 2.0f / ((float)n_global * (float)d.d_in);
         ScanRole scan = {};
         scan.cnt = (const uint32_t*)cnt; scan.offs = (uint32_t*)(wsb + ws.offs); scan.n_long = (uint32_t*)(wsb + ws.n_long);
-        scan.d_sae = d.d_sae; scan.scalars = out->scalars; scan.inv_tokens = 1.0f / (float)N;
+        scan.d_sae = d.d_sae; scan.scalars = out->scalars; scan.tokens = (float)N;
         const dim3 grid((N + 3) / 4 + 1);
 #define CALL(D)                                                                                                        \
     hipLaunchKernelGGL((sae_decode_kernel<D, 2>), grid, block, 0, stream, x, (const float*)st->W_dec, (const float*)st->b_dec, \
@@ -3145,7 +3148,7 @@ extern "C" int pv_sae_tp_finish(pv_sae_plan* plan, pv_sae_state* st, const float
         float* seg_rows = (float*)(wsb + ws.seg_rows);
         float* seg_b = (float*)(wsb + ws.seg_b);
         hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t*)cnt, offs, n_long, d.d_sae,
-                           out->scalars, 1.0f / (float)N);
+                           out->scalars, (float)N);
         hipLaunchKernelGGL(csr_post_kernel, dim3((d.d_sae + 255) / 256), block, 0, stream, (const uint32_t*)offs, chunk_start,
                            max_chunks, long_list, n_long, seg_range, max_segs, st->act_freq_scores, st->n_fwd_since_fired,
                            out->fire_count, d.d_sae, update_stats, (float*)nullptr, (float*)nullptr, sae_long_ranged(N) ? 1 : 0);
