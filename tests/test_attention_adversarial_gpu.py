@@ -3,7 +3,8 @@ the maxima on tile edges and in the ragged last tile, scores at +-1000, and rows
 are handed to the plan by hooks on attn.hook_q / hook_k / hook_v that return them: the block re-enters at PV_STAGE_QKV and
 pv_launch_attention runs with its normal dispatch.  Bounds: the module docstring of _attention_cases.  Run with ``-m gpu`` on an MI355X.
 
-The dispatch table (csrc/attention.hip, dispatch_attn), and the (dtype, d_head, T) that reach each entry here:
+The dispatch table (csrc/attention.hip, dispatch_attn; the body of attn_stream_kernel: csrc/attn_stream.hpp), and the (dtype, d_head, T)
+that reach each entry here:
 
     bf16, T <= 64, T even                       attn_wave_kernel<dh>           bf16 dh 32 / 64, T = 50, 64 (64: no cls token)
     bf16, T > 64, d_head 64                     attn_lean_kernel               bf16 dh 64, T = 65, 257, 677, 1025

@@ -1,4 +1,4 @@
-"""Wide heads on the HIP plan: ``attn_wide_kernel`` (csrc/attention_wide.hip) and the resumed attention core at 64 < d_head <= 128.
+"""Wide heads on the HIP plan: ``attn_wide_kernel`` (csrc/attention_wide.hip; its body: csrc/attn_stream.hpp) and the resumed attention core at 64 < d_head <= 128.
 Run with ``-m gpu`` on an MI355X.
 
 The row that the dispatch table in test_attention_adversarial_gpu.py cannot get (pv_launch_attention sends these shapes to their

@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
+#include "attn_stream.hpp"
 #include "prof.hpp"
 
 namespace {
@@ -279,9 +280,7 @@ int launch_attn(const AttnParams& p, hipStream_t stream) {
     }
     const dim3 grid((p.T + QB - 1) / QB, p.H, p.B), block(256);
     {
-        const double bh = (double)p.B * p.H, tt = (double)p.T * p.T;
-        const double bytes = (4.0 * bh * p.T * DH + ((p.scores ? 1.0 : 0.0) + (p.pattern ? 1.0 : 0.0)) * bh * tt) * EB;
-        ProfScope prof(PV_PROF_ATTN, stream, 4.0 * bh * tt * DH, bytes);
+        ProfScope prof = attn_prof_scope(p, EB, stream);
         hipLaunchKernelGGL((attn_kernel<T, QB, DH, MAXC>), grid, block, lds, stream, p);
     }
     PV_LAUNCH_CHECK("attn_kernel");
@@ -602,9 +601,7 @@ template <int DH>
 int launch_attn_wave(const AttnParams& p, hipStream_t stream) {
     const int heads = p.B * p.H;
     {
-        const double bh = (double)heads, tt = (double)p.T * p.T;
-        const double bytes = (4.0 * bh * p.T * DH + ((p.scores ? 1.0 : 0.0) + (p.pattern ? 1.0 : 0.0)) * bh * tt) * 2.0;
-        ProfScope prof(PV_PROF_ATTN, stream, 4.0 * bh * tt * DH, bytes);
+        ProfScope prof = attn_prof_scope(p, 2, stream);
         if (g_pv_tuning.attn_direct) hipLaunchKernelGGL((attn_wave_kernel<DH, false>), dim3((heads + 3) / 4), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((attn_wave_kernel<DH, true>), dim3((heads + 3) / 4), dim3(256), 0, stream, p);
     }
@@ -950,9 +947,7 @@ int launch_attn_lean(const AttnParams& p, hipStream_t stream) {
     int ex = 0;
     const bool pow2 = p.attn_scale > 0.f && std::frexp(p.attn_scale, &ex) == 0.5f;
     {
-        const double bh = (double)heads, tt = (double)p.T * p.T;
-        const double bytes = (4.0 * bh * p.T * p.dh + ((p.scores ? 1.0 : 0.0) + (p.pattern ? 1.0 : 0.0)) * bh * tt) * 2.0;
-        ProfScope prof(PV_PROF_ATTN, stream, 4.0 * bh * tt * p.dh, bytes);
+        ProfScope prof = attn_prof_scope(p, 2, stream);
         if (pow2) hipLaunchKernelGGL((attn_lean_kernel<64, true>), dim3(heads * qblocks), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((attn_lean_kernel<64, false>), dim3(heads * qblocks), dim3(256), 0, stream, p);
     }
@@ -962,338 +957,15 @@ int launch_attn_lean(const AttnParams& p, hipStream_t stream) {
 
 // ---------------------------------------------------------------------------------------------------
 // Streaming variant for 640 < T <= PV_ATTN_MAX_TOKENS, every (dtype, d_head) the plan supports (DINO /8: T = 785; 448 - 518 px ViTs:
-// up to 1370): the shape of attn_lean_kernel -- a WAVE owns 32 query rows of one (image, head), the four waves of a workgroup (128
-// consecutive queries) share each 32-key K / V tile through double-buffered LDS, the keys are streamed TWICE with the product
-// swapped (S^T = K Q^T: a lane holds 16 keys of ONE query) -- without that kernel's bf16 / d_head 64 specialisations, so that
-// nothing in LDS or registers grows with T:
-//   pass 1  per tile: S^T on MFMA (fp32: the f32 MFMA 32x32x2, as attn_kernel<float>), scaled + rounded to the storage dtype like
-//           the reference's score tensor, online (max, sum) per lane; the two lanes of a query are merged at the end
-//           (+ hook_attn_scores, when tapped)
-//   pass 2  the same tiles again: p = exp(s - max) / sum, rounded to the storage dtype -> hook_pattern, and z^T += V^T P^T on MFMA.
-//           The accumulator tile S^T IS the B operand of that product (its rows = keys are the sum index): register e of a lane is
-//           key (e & 3) + 8 (e >> 2) + 4 half, and the V operand is read from LDS in that key order -- fp32: one float per (key, d)
-//           of the row-major tile; bf16: two 8-byte reads of the transposed tile V^T [d][32 keys] -- no lane exchange anywhere.
-//           z^T leaves the accumulators as 4 consecutive d per register group: 16-byte (fp32) / 8-byte (bf16) stores into the
-//           query's own row.
-// A row with a NaN / +inf score, or nothing but -inf, becomes zeros (attention.py:148-150), decided per row after pass 1.
-// Taps: TW = 2 (fp32) / 4 (bf16) tiles collect in a per-wave LDS window of 32 rows x 256 B and leave as 16-byte stores, 4 rows x 256
-// contiguous bytes per instruction, at the row's own alignment (an odd T leaves rows only element-aligned); each element once.
-// LDS: K 2 x 32 x (d_head EB + 16), V the same (bf16: 2 x d_head x 80), windows 32 KB: <float, 64> 66.0 KB = two workgroups per CU,
-// the other three instances 42 - 51 KB = three.  Stated floor (tests/test_attention_long_resources_cpu.py): 2 waves per SIMD for
-// <float, 64>, 3 for <float, 32>, <bf16, 32>, <bf16, 64> (the second launch bound: without it hipcc gives <bf16, 64> 178 registers = two
-// waves); no scratch.  The fp32 instances are bound by the f32 MFMA (1/16 of the
-// bf16 rate: 2 x d_head x 32 cycles per tile and pass), the bf16 ones by VALU issue and the tap stream like attn_lean_kernel,
-// which stays the kernel of bf16 / d_head 64 (this one serves that shape only under the attn_wg override).
+// up to 1370): attn_stream_body (attn_stream.hpp) at its compile-time width, d_head == DH.  Stated floor
+// (tests/test_attention_long_resources_cpu.py): 2 waves per SIMD for <float, 64> (66 KB of LDS = two workgroups per CU), 3 for
+// <float, 32>, <bf16, 32>, <bf16, 64> (the second launch bound: without it hipcc gives <bf16, 64> 178 registers = two waves); no
+// scratch.  attn_lean_kernel stays the kernel of bf16 / d_head 64 (this one serves that shape only under the attn_wg override).
 // ---------------------------------------------------------------------------------------------------
 template <typename E, int DH>
 __global__ __launch_bounds__(256, (sizeof(E) == 4 && DH == 64) ? 2 : 3) void attn_stream_kernel(const AttnParams p) {
     static_assert(DH == 32 || DH == 64, "d_head 32 / 64");
-    constexpr int EB = DT<E>::kBytes;
-    constexpr bool F32 = EB == 4;
-    constexpr int KROW = DH * EB + 16;                       // bytes per key row of a row-major tile (+16: conflict-free b128 rows)
-    constexpr int VBYTES = F32 ? 32 * KROW : DH * L2_VROW;
-    constexpr int TW = 8 / EB;                               // tiles per tap window (256-byte rows)
-    constexpr int CH = DH * EB / 16;                         // 16-byte chunks per key row
-    constexpr int NF = (32 * CH + 255) / 256;                // chunks a thread moves per tile
-    constexpr int NTN = DH / 32;
-    constexpr int NQ = F32 ? DH / 8 : DH / 16;               // 16-byte Q fragments per lane
-    __shared__ __attribute__((aligned(16))) unsigned char Kst[2][32 * KROW];
-    __shared__ __attribute__((aligned(16))) unsigned char Vst[2][VBYTES];
-    __shared__ __attribute__((aligned(16))) unsigned char win[4][32 * 256];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int T_ = p.T, H = p.H;
-    const int qblocks = (T_ + 127) / 128;
-    int bid = blockIdx.x;                                    // whole heads per XCD, as in attn_lean_kernel
-    {
-        const int heads = p.B * H, per_xcd = heads / 8;
-        if (bid < per_xcd * 8 * qblocks) {
-            const int xcd = bid & 7, i = bid >> 3;
-            bid = ((i / qblocks) * 8 + xcd) * qblocks + i % qblocks;
-        }
-    }
-    const int g = bid / qblocks;                             // (image, head)
-    const int q0 = (bid - g * qblocks) * 128 + wave * 32;
-    const bool active = q0 < T_;                             // idle waves of a head's last block still stage tiles and meet the barriers
-    const int b = g / H, h = g - b * H;
-    const int half = lane >> 5, l31 = lane & 31;
-    unsigned char* L = win[wave];
-    const int64_t tokb = (int64_t)H * DH * EB;               // bytes between tokens of one head
-    const int64_t head_off = (((int64_t)b * T_ * H + h) * DH) * EB;
-    const unsigned char* qg = reinterpret_cast<const unsigned char*>(p.q) + head_off;
-    const unsigned char* kg = reinterpret_cast<const unsigned char*>(p.k) + head_off;
-    const unsigned char* vg = reinterpret_cast<const unsigned char*>(p.v) + head_off;
-    const int ntile = (T_ + 31) / 32;
-
-    // Q as the B operand (columns = this wave's queries).  bf16: lane (query l31, half) holds d-chunk 2 c + half; fp32: the f32
-    // MFMA sums two d per step, one per half -- the order of the sum is free, so half h takes d in [h DH / 2, (h + 1) DH / 2)
-    // (contiguous 16-byte loads) and so do the K fragments
-    uint4 qf[NQ];
-    {
-        const int qi = q0 + l31;
-#pragma unroll
-        for (int c = 0; c < NQ; ++c) {
-            const int off = F32 ? (half * (DH / 2) + 4 * c) * 4 : (2 * c + half) * 16;
-            qf[c] = qi < T_ ? *reinterpret_cast<const uint4*>(qg + qi * tokb + off) : make_uint4(0, 0, 0, 0);
-        }
-    }
-
-    // cooperative tile fetch: chunk idx = tid + 256 i -> 16 B (chunk idx / 32) of key row idx % 32; rows >= T read 0 (K: masked
-    // scores; V: 0 x 0, never 0 x garbage)
-    auto fetch = [&](const unsigned char* base, int kt, uint4 (&r)[NF]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < NF; ++i) {
-            const int idx = tid + 256 * i, key = kt * 32 + (idx & 31), ch = idx >> 5;
-            r[i] = (ch < CH && key < T_) ? *reinterpret_cast<const uint4*>(base + key * tokb + ch * 16) : make_uint4(0, 0, 0, 0);
-        }
-    };
-    auto park_rows = [&](unsigned char* dst, const uint4 (&r)[NF]) __attribute__((always_inline)) {         // row-major [32 keys][KROW]
-#pragma unroll
-        for (int i = 0; i < NF; ++i) {
-            const int idx = tid + 256 * i, key = idx & 31, ch = idx >> 5;
-            if (ch < CH) *reinterpret_cast<uint4*>(dst + key * KROW + ch * 16) = r[i];
-        }
-    };
-    auto park_v = [&](unsigned char* dst, const uint4 (&r)[NF]) __attribute__((always_inline)) {
-        if constexpr (F32) {
-            park_rows(dst, r);
-        } else {                                                             // 8 d-values of one key -> V^T[d][key] (attn_lean_kernel's stage_v)
-            const int key = tid & 31, ch = tid >> 5;
-            if (ch < CH) {
-                const uint32_t w[4] = {r[0].x, r[0].y, r[0].z, r[0].w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    *reinterpret_cast<unsigned short*>(dst + (ch * 8 + 2 * i) * L2_VROW + key * 2) = (unsigned short)(w[i] & 0xffffu);
-                    *reinterpret_cast<unsigned short*>(dst + (ch * 8 + 2 * i + 1) * L2_VROW + key * 2) = (unsigned short)(w[i] >> 16);
-                }
-            }
-        }
-    };
-
-    // S^T tile out of a K tile: sc[e] = the score of key kt * 32 + (e & 3) + 8 (e >> 2) + 4 half against query q0 + l31, scaled and
-    // rounded to the storage dtype (x * (1 / scale) is x / scale exactly when the scale is a power of two: d_head 64)
-    const float inv_scale = 1.0f / p.attn_scale;
-    const bool scale_pow2 = (__float_as_uint(p.attn_scale) & 0x007fffffu) == 0u && p.attn_scale > 0.f;
-    auto score_tile = [&](const unsigned char* kb, float (&sc)[16]) __attribute__((always_inline)) {
-        f32x16 acc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-        for (int c = 0; c < NQ; ++c) {
-            if constexpr (F32) {
-                const uint4 kf = *reinterpret_cast<const uint4*>(kb + l31 * KROW + (half * (DH / 2) + 4 * c) * 4);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(kf.x), __uint_as_float(qf[c].x), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(kf.y), __uint_as_float(qf[c].y), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(kf.z), __uint_as_float(qf[c].z), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(kf.w), __uint_as_float(qf[c].w), acc, 0, 0, 0);
-            } else {
-                const uint4 kf = *reinterpret_cast<const uint4*>(kb + l31 * KROW + (2 * c + half) * 16);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qf[c]), acc, 0, 0, 0);
-            }
-        }
-        if (scale_pow2) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sc[e] = DT<E>::round(acc[e] * inv_scale);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sc[e] = DT<E>::round(acc[e] / p.attn_scale);
-        }
-    };
-
-    // Taps: a lane's four groups of 4 consecutive keys go into the wave's LDS window [32 rows][TW tiles x 32 keys] (16-byte chunk c
-    // of row r at position c ^ (r & 15)); every TW-th tile (and after the last) the window leaves as 16-byte stores
-    auto tap_put = [&](int kt, const float (&v)[16]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            if constexpr (F32) {
-                const int c = (kt & (TW - 1)) * 8 + 2 * g4 + half;
-                *reinterpret_cast<float4*>(L + l31 * 256 + ((c ^ (l31 & 15)) * 16)) = make_float4(v[4 * g4], v[4 * g4 + 1], v[4 * g4 + 2], v[4 * g4 + 3]);
-            } else {
-                const int c = (kt & (TW - 1)) * 4 + g4;
-                *reinterpret_cast<uint2*>(L + l31 * 256 + ((c ^ (l31 & 15)) * 16) + 8 * half) =
-                    make_uint2(pack_bf16x2(v[4 * g4], v[4 * g4 + 1]), pack_bf16x2(v[4 * g4 + 2], v[4 * g4 + 3]));
-            }
-        }
-    };
-    const int st_row = lane >> 4, st_ch = lane & 15;
-    auto tap_flush = [&](unsigned char* dst, int kt) __attribute__((always_inline)) {
-        if ((kt & (TW - 1)) != TW - 1 && kt + 1 < ntile) return;
-        __builtin_amdgcn_wave_barrier();
-        const int k0 = (kt & ~(TW - 1)) * 32;                                // first key of the window
-        const int nb = min(256, (T_ - k0) * EB);                             // valid bytes per row
-#pragma unroll 2
-        for (int it = 0; it < 8; ++it) {
-            const int row = st_row + 4 * it;
-            if (q0 + row < T_ && st_ch * 16 < nb) {
-                const unsigned char* src = L + row * 256 + ((st_ch ^ (row & 15)) * 16);
-                unsigned char* d = dst + ((int64_t)(q0 + row) * T_ + k0) * EB + st_ch * 16;
-                if (st_ch * 16 + 16 <= nb) {
-                    const uint4 r = *reinterpret_cast<const uint4*>(src);
-                    using V = std::conditional_t<F32, pv_u32x4_a4, pv_u32x4_a2>;
-                    pv_store16_as<PV_ST_PLAIN, V>(d, r.x, r.y, r.z, r.w);
-                } else {
-                    for (int e = 0; e < (nb - st_ch * 16) / EB; ++e)
-                        reinterpret_cast<E*>(d)[e] = reinterpret_cast<const E*>(src)[e];
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    auto key_masked = [&](int kt, int e) __attribute__((always_inline)) { return kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * half >= T_; };
-
-    // ---- pass 1: online max / sum (and the score tap)
-    unsigned char* sc_dst = p.scores ? reinterpret_cast<unsigned char*>(p.scores) + (int64_t)g * T_ * T_ * EB : nullptr;
-    float m = -INFINITY, l = 0.f;
-    auto pass1_tile = [&](int kt) __attribute__((always_inline)) {
-        float sc[16];
-        score_tile(Kst[kt & 1], sc);
-        if (sc_dst) tap_put(kt, sc);
-        if (kt + 1 == ntile) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                if (key_masked(kt, e)) sc[e] = -INFINITY;
-        }
-        float tm = sc[0];
-#pragma unroll
-        for (int e = 1; e < 16; ++e) tm = fmaxf(tm, sc[e]);
-        const float mn = fmaxf(m, tm);
-        const float mb = mn == -INFINITY ? 0.f : mn;                          // nothing but -inf so far: exp(-inf - 0) = 0, not exp(NaN)
-        float sum = 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sum += __expf(sc[e] - mb);
-        l = l * __expf(m - mb) + sum;
-        m = mn;
-    };
-    uint4 kn1[NF], kn2[NF];
-    fetch(kg, 0, kn2);
-    fetch(kg, 1, kn1);
-    park_rows(Kst[0], kn2);
-    // per tile, as in attn_lean_kernel: issue the fetch of tile kt + 2 -> multiply tile kt out of LDS -> park tile kt + 1 in the other
-    // buffer (free since the barrier that ended tile kt - 1) -> flush the tap window when it is due -> barrier
-    __syncthreads();
-    for (int kt = 0; kt < ntile; ++kt) {
-        fetch(kg, kt + 2, kn2);
-        if (active) pass1_tile(kt);
-        park_rows(Kst[(kt + 1) & 1], kn1);
-        if (active && sc_dst) tap_flush(sc_dst, kt);
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NF; ++i) kn1[i] = kn2[i];
-    }
-    {   // merge the two lanes of a query
-        const float mo = __shfl_xor(m, 32, 64), lo = __shfl_xor(l, 32, 64);
-        const float M = fmaxf(m, mo);
-        const float Mb = M == -INFINITY ? 0.f : M;
-        l = l * __expf(m - Mb) + lo * __expf(mo - Mb);
-        m = M;
-    }
-    // a row with an infinite / NaN score (or none at all) is NaN throughout in the reference -> zeros (attention.py:149)
-    const bool row_ok = l > 0.f && l < INFINITY && m > -INFINITY && m < INFINITY;
-    const float inv_l = row_ok ? 1.0f / l : 0.f;
-    const float mrow = row_ok ? m : 0.f;
-
-    // ---- pass 2: pattern tap + z
-    unsigned char* pt_dst = p.pattern ? reinterpret_cast<unsigned char*>(p.pattern) + (int64_t)g * T_ * T_ * EB : nullptr;
-    f32x16 zacc[NTN];
-#pragma unroll
-    for (int tn = 0; tn < NTN; ++tn)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) zacc[tn][e] = 0.f;
-    auto pass2_tile = [&](int kt) __attribute__((always_inline)) {
-        float pr[16];
-        score_tile(Kst[kt & 1], pr);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float x = DT<E>::round(__expf(pr[e] - mrow) * inv_l);       // attention.py:152 pattern.to(cfg.dtype)
-            pr[e] = row_ok ? x : 0.f;
-        }
-        if (kt + 1 == ntile) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                if (key_masked(kt, e)) pr[e] = 0.f;
-        }
-        if (pt_dst) tap_put(kt, pr);
-        const unsigned char* vb = Vst[kt & 1];
-        if constexpr (F32) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int key = (e & 3) + 8 * (e >> 2) + 4 * half;
-#pragma unroll
-                for (int tn = 0; tn < NTN; ++tn) {
-                    const float vv = *reinterpret_cast<const float*>(vb + key * KROW + (tn * 32 + l31) * 4);
-                    zacc[tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv, pr[e], zacc[tn], 0, 0, 0);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                // element j of this lane's fragment = register 8 s + j = key 16 s + 8 (j >> 2) + 4 half + (j & 3)
-                const u32x4_t pb = {pack_bf16x2(pr[8 * s], pr[8 * s + 1]), pack_bf16x2(pr[8 * s + 2], pr[8 * s + 3]),
-                                    pack_bf16x2(pr[8 * s + 4], pr[8 * s + 5]), pack_bf16x2(pr[8 * s + 6], pr[8 * s + 7])};
-#pragma unroll
-                for (int tn = 0; tn < NTN; ++tn) {
-                    const unsigned char* vr = vb + (tn * 32 + l31) * L2_VROW + (16 * s + 4 * half) * 2;
-                    const uint2 lo = *reinterpret_cast<const uint2*>(vr), hi = *reinterpret_cast<const uint2*>(vr + 16);
-                    const u32x4_t va = {lo.x, lo.y, hi.x, hi.y};
-                    zacc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, va), __builtin_bit_cast(bf16x8, pb), zacc[tn], 0, 0, 0);
-                }
-            }
-        }
-    };
-    uint4 vn1[NF], vn2[NF];
-    fetch(kg, 0, kn2);
-    fetch(vg, 0, vn2);
-    fetch(kg, 1, kn1);
-    fetch(vg, 1, vn1);
-    park_rows(Kst[0], kn2);        // (everyone left pass 1's last tile through its closing barrier)
-    park_v(Vst[0], vn2);
-    __syncthreads();
-    for (int kt = 0; kt < ntile; ++kt) {
-        fetch(kg, kt + 2, kn2);
-        fetch(vg, kt + 2, vn2);
-        if (active) pass2_tile(kt);
-        park_rows(Kst[(kt + 1) & 1], kn1);
-        park_v(Vst[(kt + 1) & 1], vn1);
-        if (active && pt_dst) tap_flush(pt_dst, kt);
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NF; ++i) {
-            kn1[i] = kn2[i];
-            vn1[i] = vn2[i];
-        }
-    }
-    if (!active) return;
-
-    // ---- z [B, T, H, dh]: zacc[tn][e] = z[query q0 + l31][d = 32 tn + (e & 3) + 8 (e >> 2) + 4 half]
-    const int qi = q0 + l31;
-    if (qi < T_) {
-        unsigned char* zr = reinterpret_cast<unsigned char*>(p.z) + head_off + qi * tokb;
-#pragma unroll
-        for (int tn = 0; tn < NTN; ++tn)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int d0 = 32 * tn + 8 * g4 + 4 * half;
-                const float a0 = zacc[tn][4 * g4], a1 = zacc[tn][4 * g4 + 1], a2 = zacc[tn][4 * g4 + 2], a3 = zacc[tn][4 * g4 + 3];
-                if constexpr (F32) *reinterpret_cast<float4*>(zr + d0 * 4) = make_float4(a0, a1, a2, a3);
-                else *reinterpret_cast<uint2*>(zr + d0 * 2) = make_uint2(pack_bf16x2(a0, a1), pack_bf16x2(a2, a3));
-            }
-    }
-}
-
-template <typename E, int DH>
-int launch_attn_stream(const AttnParams& p, hipStream_t stream) {
-    constexpr int EB = DT<E>::kBytes;
-    const int64_t blocks = (int64_t)p.B * p.H * ((p.T + 127) / 128);
-    PV_REQUIRE(blocks < (1ll << 31), "attention grid");
-    PV_REQUIRE(pv_aligned16(p.z), "attention output must be 16-byte aligned");
-    {
-        const double bh = (double)p.B * p.H, tt = (double)p.T * p.T;
-        const double bytes = (4.0 * bh * p.T * DH + ((p.scores ? 1.0 : 0.0) + (p.pattern ? 1.0 : 0.0)) * bh * tt) * EB;
-        ProfScope prof(PV_PROF_ATTN, stream, 4.0 * bh * tt * DH, bytes);
-        hipLaunchKernelGGL((attn_stream_kernel<E, DH>), dim3((unsigned)blocks), dim3(256), 0, stream, p);
-    }
-    PV_LAUNCH_CHECK("attn_stream_kernel");
-    return PV_OK;
+    attn_stream_body<E, DH, false>(p);
 }
 
 template <typename T>
@@ -1322,8 +994,8 @@ int dispatch_attn(AttnParams& p, hipStream_t stream) {
         if (p.dh == 32) return launch_attn<T, 32, 32, 10>(p, stream);
     } else if (p.T <= PV_ATTN_MAX_TOKENS) {
         // beyond the [32][Tpad] LDS strip of attn_kernel (bf16 / d_head 64 went to attn_lean_kernel above unless attn_wg asks otherwise)
-        if (p.dh == 64) return launch_attn_stream<T, 64>(p, stream);
-        if (p.dh == 32) return launch_attn_stream<T, 32>(p, stream);
+        if (p.dh == 64) return launch_attn_streaming<T>(attn_stream_kernel<T, 64>, "attn_stream_kernel", p, stream);
+        if (p.dh == 32) return launch_attn_streaming<T>(attn_stream_kernel<T, 32>, "attn_stream_kernel", p, stream);
     }
     pv_set_error("attention: unsupported (T, d_head); supported: T <= " PV_STR(PV_ATTN_MAX_TOKENS)
                  ", d_head in {32, 64} or 64 < d_head <= 128 with d_head % 8 == 0");
