@@ -84,7 +84,7 @@ def gamma(m):
 
 
 def long_ranged(n):
-    """sae_long_ranged of csrc/sae.hip: the token-range form sorts a list through an n x 4-byte LDS array"""
+    """sae_long_ranged of csrc/sae_bwd.hip: the token-range form sorts a list through an n x 4-byte LDS array"""
     return n * 4 + 4096 <= 150 * 1024
 
 
@@ -566,9 +566,9 @@ def _seqsum(rows):
 
 
 def twin(P, x, idx, val, norm, n_global=None, l1=0.0, slip=None, out=None, sparse_grads=False, ranged=None, list_perm=None):
-    """The step behind the selection in float32, structured as csrc/sae.hip: prep, decode, CSR by feature, chunk cuts, short walk, long
-    lists in the token-range or the count-cut form, segment combine, zeroing of empty rows, gb_dec.  out: the gradient buffers to write
-    into (what is not stored stays as it was; default: NaN).  ranged: force a segment form (default: the kernels' choice by n).
+    """The step behind the selection in float32, structured as csrc/sae.hip (prep, decode, gb_dec) and csrc/sae_bwd.hip (CSR by feature,
+    chunk cuts, short walk, long lists in the token-range or the count-cut form, segment combine, zeroing of empty rows).  out: the
+    gradient buffers to write into (what is not stored stays as it was; default: NaN).  ranged: force a segment form (default: the kernels' choice by n).
     list_perm: RandomState shuffling the pairs of the unsorted (count-cut) long lists, as the selection's atomics may.  slip: one of SLIPS."""
     assert slip is None or slip in SLIPS, slip
     P = {k_: np.asarray(v, F32) for k_, v in P.items()}

@@ -114,9 +114,9 @@ def test_step_on_planted_classes(name, tuning):
                   eng, rep_rows)
 
 
-def same_bits(label, a, b, ranged, eng, rep_rows):
+def same_bits(label, a, b, ranged, eng, rep_rows, names=("sae_out", "fire_count", "index sets")):
     g_same = torch.equal(a[0], b[0])
-    for i, what in ((1, "sae_out"), (3, "fire_count"), (4, "index sets")):
+    for i, what in zip((1, 3, 4), names):
         assert torch.equal(a[i], b[i]), f"{label}: {what}"
     assert torch.equal(a[2][:3], b[2][:3]), f"{label}: loss / l0"
     if ranged:
@@ -134,7 +134,9 @@ def same_bits(label, a, b, ranged, eng, rep_rows):
 @pytest.mark.parametrize("name", SC.PATTERNS)
 def test_tp_finish_on_injected_pairs(name, d_in, tuning):
     """encode_topk -> tp_partial(renorm_decoder=False) -> tp_finish on a one-rank shard with the pairs of the pattern (LayerNorm on, the
-    decoder renormed beforehand, update_stats on), folded and in single launches.  A negative value is a hole: it must contribute nothing."""
+    decoder renormed beforehand, update_stats on), folded and in single launches.  A negative value is a hole: it must contribute nothing.
+    The two launch forms run the same code behind the decode launch (sae_csr_build with and without ``folded``), the loss included: what
+    they leave is compared by ``same_bits`` -- every bit in the token-range form, the short lists' rows and the scalars in the count-cut form."""
     c = SC.injected(name, d_in)
     n = c.n
     eng = engine(c)
@@ -144,6 +146,7 @@ def test_tp_finish_on_injected_pairs(name, d_in, tuning):
     counts = ref["counts"]
     assert np.array_equal(counts, c.lengths) and int((c.val < 0).sum()) == min(5, c.holes)
     x, idx, val = torch.from_numpy(c.x).cuda(), torch.from_numpy(c.idx.copy()).cuda(), torch.from_numpy(c.val.copy()).cuda()
+    kept = {}
     for fold in (1, 0):
         tuning("sae_fold", fold)
         eng.encode_topk(x, want_ln_stats=False)
@@ -155,6 +158,10 @@ def test_tp_finish_on_injected_pairs(name, d_in, tuning):
         got["partial"] = pre.cpu().numpy()
         ratios, msgs = SC.check(ref, got, poison="dense")
         verdict(f"tp_finish {name} d_in={d_in} fold={fold}", ratios, msgs)
+        kept[fold] = (bits(eng.flat_g).clone(), eng.act_freq_scores.clone(), eng.scalars[:3].clone(), eng.fire_count.clone(),
+                      eng.n_fwd_since_fired.clone())
+    same_bits(f"tp_finish {name} d_in={d_in} folded against single launches", kept[1], kept[0], SC.long_ranged(n), eng,
+              torch.from_numpy(counts <= SC.BWD_LMAX).cuda(), names=("act_freq_scores", "fire_count", "n_fwd_since_fired"))
 
 
 @pytest.mark.parametrize("cap", [8, 12])

@@ -1,4 +1,4 @@
-// Shared definitions of the SAE step (sae.hip: prep / decode / backward / Adam; sae_enc.hip: the encoder + top-k).
+// Shared definitions of the SAE step (sae.hip: prep / decode / Adam; sae_bwd.hip: the sparse backward; sae_enc.hip: the encoder + top-k).
 #pragma once
 #include "gemm.hpp"
 #include "prof.hpp"
@@ -23,6 +23,15 @@ struct pv_sae_plan {
 struct SaePre {
     const float* x; int d_true; bool have_mean;
 };
+
+// kernels whose lanes own 16-byte column groups: d_in <= 256 * V4
+#define V4_DISPATCH(d_in, CALL)             \
+    do {                                    \
+        if ((d_in) <= 256) { CALL(1); }     \
+        else if ((d_in) <= 768) { CALL(3); } \
+        else if ((d_in) <= 1024) { CALL(4); } \
+        else { CALL(5); }                   \
+    } while (0)
 
 struct SaeWs {
     size_t total;
@@ -241,7 +250,8 @@ constexpr int PV_SAE_RELU_CAP_MAX = 256;     // kept activations per token the s
 static inline bool pv_sae_relu_sparse_ok(const pv_sae_desc& d) {
     return d.d_sae % 256 == 0 && d.d_sae >= 2048 && d.d_in % 8 == 0 && d.d_in >= 32 && !g_pv_tuning.sae_exact;
 }
-struct SaeTail {                             // the k-dependent buffers of sae_sparse_tail
+struct SaeTail {                             // the k-dependent buffers of the sparse backward (sae_bwd.hpp: sae_tail, relu_tail); dh [N k]: the
+                                             // gradient at the kept activations, written by the decode kernel
     float* dh; uint32_t* chunk_start; uint32_t* wpos; uint32_t* seg_range; float* seg_rows; float* seg_b; int32_t* pairs;
     int max_segs;
 };
@@ -255,12 +265,6 @@ int sae_encode_relu(const pv_sae_desc& d, const pv_sae_state* st, int N, int cap
                     float* l1part, uint32_t* cand_cnt, void* cand, uint32_t* feat_cnt, uint32_t* wpos, uint32_t* mode,
                     const float* prev_scalars, unsigned char* wsb, const SaeWs& ws, hipStream_t stream, float* l0part = nullptr,
                     float* valg = nullptr);
-// sae.hip: the backward of a k-sparse step behind its decode kernel (see the definition)
-int sae_csr_backward(pv_sae_plan* plan, pv_sae_state* st, int N, int k, const int32_t* topk_idx, const float* topk_val, const float* dh,
-                     const float* dY, const float* sae_in, float* scalars, float* fire_count, int update_stats, bool sparse,
-                     const SaeTail& tb, unsigned char* wsb, const SaeWs& ws, const float* loss_part, float loss_scale, bool cs_here,
-                     const uint32_t* gate, hipStream_t stream, const float* val_b = nullptr, const float* dYb = nullptr,
-                     const uint32_t* cnt_in = nullptr);
 // sae.hip: the gated step in sparse form (pv_sae_gated_step_sparse; see the definition)
 struct GatedSparseWs {
     ReluWs rw;

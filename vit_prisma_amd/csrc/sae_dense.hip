@@ -28,6 +28,7 @@
 #include <algorithm>
 #include "kloop.hpp"
 #include "sae.hpp"
+#include "sae_bwd.hpp"
 #include <cstring>
 
 namespace {
@@ -1328,12 +1329,8 @@ extern "C" int pv_sae_relu_step(pv_sae_plan* plan, pv_sae_state* st, const float
                                  (uint32_t*)(wsb + ws.cnt), (uint32_t*)(rwb + rw.wpos), mode, (const float*)out->scalars, wsb, ws, stream);
             if (rc) return rc;
         }
-        SaeTail tb;
-        tb.dh = (float*)(rwb + rw.dh); tb.chunk_start = (uint32_t*)(rwb + rw.cursor); tb.wpos = (uint32_t*)(rwb + rw.wpos);
-        tb.seg_range = (uint32_t*)(rwb + rw.seg_range); tb.seg_rows = (float*)(rwb + rw.seg_rows); tb.seg_b = (float*)(rwb + rw.seg_b);
-        tb.pairs = (int32_t*)(rwb + rw.pairs); tb.max_segs = rw.max_segs;
         rc = sae_sparse_tail(plan, st, x, N, n_global, cap, idx, val, out->sae_out, out->scalars, out->fire_count, update_stats,
-                             sparse_grads, defer ? (const float*)st->dec_inv_norm : (const float*)nullptr, tb, wsb, ws,
+                             sparse_grads, defer ? (const float*)st->dec_inv_norm : (const float*)nullptr, relu_tail(rwb, rw), wsb, ws,
                              tc ? (const float*)st->tc.target : x, tc ? (const float*)st->tc.b_dec_out : (const float*)st->b_dec, skip, tc,
                              l1_coefficient / (float)n_global, tok_cnt, mode, stream, /*bias_grads*/ false);
         if (rc) return rc;
