@@ -47,7 +47,10 @@ extern "C" {
  * gemm_persist / gemm_stagger tuning keys; 22: pv_sae_desc.activation / lp_norm,
  * normalize_layer_norm = 2 (constant_norm_rescale), the split-fp16 dense GEMMs and their tuning key dense_fp32, gemm_cus;
  * 24: pv_vit_desc.pooling, PV_ATTN_MAX_TOKENS = 2048 (was 640);
- * 25: the supported attention shapes gain the wide heads, 64 < d_head <= 128 with d_head % 8 == 0 (CLIP ViT-H / g / bigG-14)). */
+ * 25: the supported attention shapes gain the wide heads, 64 < d_head <= 128 with d_head % 8 == 0 (CLIP ViT-H / g / bigG-14)).
+ * Purely ADDITIVE exports do not bump it: the text tower (pv_text_desc, pv_text_weights, pv_text_plan_create,
+ * pv_text_plan_set_weights, pv_text_forward) and pv_attention arrived at 25 and left every existing struct layout, signature, slot
+ * value and flag as it was, so a caller written against 25 runs unchanged; the Python binding checks the build id besides. */
 #define PV_ABI_VERSION 25
 int pv_abi_version(void);
 /* Hash of the sources this binary was built from (sha256 over the .hip / .hpp files of vit_prisma_amd/csrc and this header, names and
@@ -246,7 +249,58 @@ int pv_vit_forward_stage(pv_vit_plan* plan, const void* images, const void* resi
                          int32_t exit_stage, int32_t run_head, const pv_tap* taps, int32_t n_taps, void* workspace,
                          size_t workspace_bytes, void* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Text tower (HookedTextTransformer.forward, models/base_text_transformer.py:119-160): token    */
+/* embedding + position, the SAME blocks under a causal mask, ln_final, the EOT row, head       */
+/* ------------------------------------------------------------------------------------------ */
+
+typedef struct pv_text_desc {
+    int32_t n_layers, d_model, n_heads, d_head, d_mlp;
+    int32_t context_length;    /* tokens per prompt (CLIP: 77); <= PV_ATTN_MAX_TOKENS          */
+    int32_t vocab_size;        /* rows of token_embed                                         */
+    int32_t n_classes;         /* head width; ignored when has_head == 0                      */
+    int32_t has_head;          /* return_type != "pre_logits", base_text_transformer.py:153   */
+    int32_t normalize_output;  /* F.normalize(dim=-1), base_text_transformer.py:157-158       */
+    int32_t causal;            /* the attn_mask buffer exists (no_causal_mask == False), :92-98, 188-194; needs d_head in {32, 64} */
+    int32_t activation;        /* PV_ACT_*                                                    */
+    int32_t dtype;             /* PV_DTYPE_*                                                  */
+    float eps;                 /* LayerNorm eps                                               */
+    float attn_scale;          /* sqrt(d_head) or 1, models/layers/attention.py:96-99         */
+} pv_text_desc;
+
+typedef struct pv_text_weights {
+    const void *token_embed;               /* [vocab, d]  token_embed.weight, base_text_transformer.py:48 */
+    const void *pos_embed;                 /* [T, d]      :53                                */
+    const void *ln_final_w, *ln_final_b;   /* [d]                                            */
+    const void *W_H, *b_H;                 /* [d, n_classes], [n_classes]  head.py:20-25     */
+    const pv_vit_layer_weights* layers;    /* HOST array of n_layers entries                 */
+} pv_text_weights;
+
+/* Replaces HookedTextTransformer.__init__'s shape bookkeeping (base_text_transformer.py:27-106).  The plan is a pv_vit_plan:
+ * pv_vit_plan_destroy, pv_vit_shadow_bytes and pv_vit_workspace_bytes serve it; the forward entries do not mix (a text plan handed
+ * to pv_vit_forward*, or a vision plan to pv_text_forward, is PV_ERR_INVALID before any launch).
+ * Rules: context_length <= PV_ATTN_MAX_TOKENS; causal: d_head in {32, 64}; causal == 0: the attention shapes of pv_vit_plan_create;
+ * d_model % 8 == 0, d_model <= 2048. */
+int pv_text_plan_create(const pv_text_desc* desc, pv_vit_plan** out_plan);
+/* As pv_vit_plan_set_weights (the per-layer shadows are the same). */
+int pv_text_plan_set_weights(pv_vit_plan* plan, const pv_text_weights* w, void* shadow, size_t shadow_bytes, void* stream);
+/* HookedTextTransformer.forward (base_text_transformer.py:119-160) + run_with_cache's caching hooks.
+ *   tokens         [B, context_length] int64 ids.  An id outside [0, vocab_size) reads no memory: its hook_embed / hook_full_embed
+ *                  rows are NaN (nn.Embedding device-asserts there)
+ *   run_head       0: stop after the blocks; 1: ln_final, the row at the FIRST maximal id (tokens.argmax(dim=-1), :151), head
+ *                  (+ normalise) -> out [B, n_classes] (or [B, d] without head)
+ * Slots: PV_SLOT_EMBED is [B, T, d] here; PV_SLOT_FULL_EMBED is hook_full_embed == blocks.0.hook_resid_pre (the reference passes the
+ * same tensor on); PV_SLOT_LNF_*, PV_SLOT_HEAD_OUT and the per-layer slots as for the ViT; the PV_SLOT_LNPRE_* slots are refused
+ * (ln_pre never runs, :139-146).  Without an ln_final tap, ln_final runs on the B pooled rows only. */
+int pv_text_forward(pv_vit_plan* plan, const int64_t* tokens, int32_t batch, int32_t run_head, const pv_tap* taps, int32_t n_taps,
+                    void* workspace, size_t workspace_bytes, void* out, void* stream);
+
 /* Kernel-level entry points (used by the unit tests and by bench.py's roofline leg). */
+/* The attention core alone (models/layers/attention.py:135-153, 246-281): q, k, v, z [B, T, H, dh], scores / pattern [B, H, T, T] or
+ * NULL, all of dtype T; causal != 0 adds -inf where key > query to the scaled scores (base_text_transformer.py:188-194), d_head in
+ * {32, 64} only.  Goes straight to the dispatch the plans use. */
+int pv_attention(int32_t dtype, const void* q, const void* k, const void* v, int32_t B, int32_t T, int32_t H, int32_t dh,
+                 float attn_scale, int32_t causal, void* scores, void* pattern, void* z, void* stream);
 /* C[M,N] = A[M,K] @ Bt[N,K]^T + bias[N]; dtype T for A, Bt, bias, C. */
 int pv_gemm_bias(int32_t dtype, const void* A, int64_t lda, const void* Bt, int64_t ldb,
                  const void* bias, void* C, int64_t ldc, int32_t M, int32_t N, int32_t K,

@@ -6,16 +6,18 @@ The arithmetic of the hot path lives in libpvnative.so (hand-written HIP for gfx
 include/pv_native.h); this package is the host-side mirror of the reference's Python interface.
 """
 from .activation_cache import ActivationCache
-from .configs import HookedViTConfig
+from .configs import HookedTextTransformerConfig, HookedViTConfig
 from .hook_points import HookPoint, LensHandle
 from .hooked_root_module import HookedRootModule
 from .compat import install_as
 from .vit import (Attention, Head, HookedViT, LayerNorm, LayerNormPre, MLP, PatchEmbedding, PosEmbedding,
                   TransformerBlock)
 from .sae_vit import HookedSAEViT
+from .text import HookedTextTransformer
 
 __all__ = [
     "ActivationCache", "HookedViTConfig", "HookPoint", "LensHandle", "HookedRootModule", "HookedViT", "HookedSAEViT",
+    "HookedTextTransformer", "HookedTextTransformerConfig",
     "Attention", "Head", "LayerNorm", "LayerNormPre", "MLP", "PatchEmbedding", "PosEmbedding",
     "TransformerBlock", "install_as",
 ]

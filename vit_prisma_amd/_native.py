@@ -57,6 +57,19 @@ class VitWeights(C.Structure):
         "W_H", "b_H")] + [("layers", C.POINTER(VitLayerWeights))]
 
 
+class TextDesc(C.Structure):
+    """pv_text_desc"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "n_layers", "d_model", "n_heads", "d_head", "d_mlp", "context_length", "vocab_size", "n_classes", "has_head",
+        "normalize_output", "causal", "activation", "dtype")] + [("eps", C.c_float), ("attn_scale", C.c_float)]
+
+
+class TextWeights(C.Structure):
+    """pv_text_weights"""
+    _fields_ = [(n, C.c_void_p) for n in ("token_embed", "pos_embed", "ln_final_w", "ln_final_b", "W_H", "b_H")] + [
+        ("layers", C.POINTER(VitLayerWeights))]
+
+
 class Tap(C.Structure):
     _fields_ = [("slot", C.c_int32), ("layer", C.c_int32), ("dst", C.c_void_p)]
 
@@ -108,7 +121,8 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "pv_abi_version", "pv_build_id", "pv_last_error",
     "pv_vit_plan_create", "pv_vit_plan_destroy", "pv_vit_shadow_bytes", "pv_vit_plan_set_weights",
-    "pv_vit_workspace_bytes", "pv_vit_forward", "pv_vit_forward_from", "pv_vit_forward_seg", "pv_vit_forward_stage", "pv_gemm_bias", "pv_gemm_epilogue", "pv_transpose_batched",
+    "pv_vit_workspace_bytes", "pv_vit_forward", "pv_vit_forward_from", "pv_vit_forward_seg", "pv_vit_forward_stage",
+    "pv_text_plan_create", "pv_text_plan_set_weights", "pv_text_forward", "pv_attention", "pv_gemm_bias", "pv_gemm_epilogue", "pv_transpose_batched",
     "pv_prof_enable", "pv_prof_reset", "pv_prof_read", "pv_prof_read_tag",
     "pv_sae_plan_create", "pv_sae_plan_destroy", "pv_sae_workspace_bytes", "pv_sae_renorm_decoder",
     "pv_sae_step", "pv_sae_grad_sqnorm", "pv_sae_grad_sqnorm_step", "pv_sae_grad_sqnorm_rows", "pv_sae_apply", "pv_sae_encode_topk",
@@ -159,6 +173,10 @@ def lib() -> C.CDLL:
     L.pv_vit_forward_from.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(Tap), i32, vp, sz, vp, vp]
     L.pv_vit_forward_seg.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Tap), i32, vp, sz, vp, vp]
     L.pv_vit_forward_stage.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Tap), i32, vp, sz, vp, vp]
+    L.pv_text_plan_create.argtypes = [C.POINTER(TextDesc), C.POINTER(vp)]
+    L.pv_text_plan_set_weights.argtypes = [vp, C.POINTER(TextWeights), vp, sz, vp]
+    L.pv_text_forward.argtypes = [vp, vp, i32, i32, C.POINTER(Tap), i32, vp, sz, vp, vp]
+    L.pv_attention.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp, vp]
     L.pv_gemm_bias.argtypes = [i32, vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, vp]
     L.pv_gemm_epilogue.argtypes = [i32, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp]
     L.pv_transpose_batched.argtypes = [i32, vp, vp, i32, i32, i32, vp]

@@ -6,7 +6,7 @@
     from vit_prisma.sae.config import VisionModelSAERunnerConfig
 
 Registers ``sys.modules`` aliases for the reference's import paths that sit on the hot path
-(/root/reference/src/vit_prisma/{models/base_vit (HookedViT, HookedSAEViT), models/model_loader (offline form), models/layers/*, configs/HookedViTConfig,
+(/root/reference/src/vit_prisma/{models/base_vit (HookedViT, HookedSAEViT), models/base_text_transformer (HookedTextTransformer), configs/HookedTextTransformerConfig, models/model_loader (offline form), models/layers/*, configs/HookedViTConfig,
 prisma_tools/{hook_point, hooked_root_module, activation_cache, lens_handle}, sae/{config, sae,
 train_sae}, sae/training/{activations_store, geometric_median, get_scheduler}}.py).  Reference SAE
 checkpoints pickle ``vit_prisma.sae.config.VisionModelSAERunnerConfig`` inside the ``.pt``
@@ -45,7 +45,7 @@ def install_as(name: str = "vit_prisma", force: bool = False) -> None:
     if existing is not None and not getattr(existing, "_pv_alias", False) and not force:
         raise RuntimeError(f"a real '{name}' package is already imported; pass force=True to shadow it")
     import vit_prisma_amd as A
-    from . import activation_cache, configs, hook_points, hooked_root_module, model_loader, utils as U, vit
+    from . import activation_cache, configs, hook_points, hooked_root_module, model_loader, text, utils as U, vit
     from .sae import config as sae_config, geometric_median, get_scheduler, sae as sae_mod, store, trainer, variants
 
     layers = dict(
@@ -56,11 +56,13 @@ def install_as(name: str = "vit_prisma", force: bool = False) -> None:
         "": (True, _public(A, A.__all__)),
         "models": (True, {}),
         "models.base_vit": (False, {**_public(vit), "HookedSAEViT": A.HookedSAEViT}),
+        "models.base_text_transformer": (False, _public(text, ["HookedTextTransformer", "HookedTextTransformerConfig"])),
         "models.model_loader": (False, _public(model_loader, ["load_hooked_model", "load_config", "list_available_models"])),
         "models.layers": (True, {}),
         **{f"models.layers.{k}": (False, v) for k, v in layers.items()},
-        "configs": (True, _public(configs, ["HookedViTConfig"])),
+        "configs": (True, _public(configs, ["HookedViTConfig", "HookedTextTransformerConfig"])),
         "configs.HookedViTConfig": (False, _public(configs)),
+        "configs.HookedTextTransformerConfig": (False, _public(configs)),
         "prisma_tools": (True, {}),
         "prisma_tools.hook_point": (False, _public(hook_points, ["HookPoint"])),
         "prisma_tools.lens_handle": (False, _public(hook_points, ["LensHandle"])),

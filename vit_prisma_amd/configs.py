@@ -121,3 +121,11 @@ class HookedViTConfig:
 
     def to_dict(self) -> Dict[str, Any]:
         return {f.name: getattr(self, f.name) for f in fields(self)}
+
+
+@dataclass
+class HookedTextTransformerConfig(HookedViTConfig):
+    """Config of HookedTextTransformer (the reference's configs/HookedTextTransformerConfig.py:10-15): the ViT's fields plus the
+    two the text tower needs."""
+    context_length: int = 77
+    vocab_size: int = 10_000

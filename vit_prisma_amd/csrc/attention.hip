@@ -965,7 +965,7 @@ int launch_attn_lean(const AttnParams& p, hipStream_t stream) {
 template <typename E, int DH>
 __global__ __launch_bounds__(256, (sizeof(E) == 4 && DH == 64) ? 2 : 3) void attn_stream_kernel(const AttnParams p) {
     static_assert(DH == 32 || DH == 64, "d_head 32 / 64");
-    attn_stream_body<E, DH, false>(p);
+    attn_stream_body<E, DH, false, false>(p);
 }
 
 template <typename T>
@@ -1069,6 +1069,8 @@ int pv_launch_attention(int dtype, AttnParams p, hipStream_t stream) {
     PV_REQUIRE(p.q && p.k && p.v && p.z, "attention operands must be non-null");
     PV_REQUIRE(pv_aligned16(p.q) && pv_aligned16(p.k) && pv_aligned16(p.v), "attention operands must be 16-byte aligned");
     PV_REQUIRE(p.B <= 65535 && p.H <= 65535, "attention grid limits");
+    // the causal mask lives in attn_causal_kernel alone (attention_causal.hip), at every T; none of the kernels below knows it
+    if (p.causal) return pv_launch_attention_causal(dtype, p, stream);
     // wide heads (64 < d_head <= 128): attn_wide_kernel (attention_wide.hip) at every T, before the table of d_head 32 / 64
     if (p.dh > 64) return pv_launch_attention_wide(dtype, p, stream);
     if (dtype == PV_DTYPE_BF16) return dispatch_attn<bf16_t>(p, stream);

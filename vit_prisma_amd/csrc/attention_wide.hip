@@ -14,7 +14,7 @@ namespace {
 template <typename E, int DHP>
 __global__ __launch_bounds__(256, sizeof(E) == 4 ? 1 : 2) void attn_wide_kernel(const AttnParams p) {
     static_assert(DHP == 96 || DHP == 128, "padded d_head 96 / 128");
-    attn_stream_body<E, DHP, true>(p);
+    attn_stream_body<E, DHP, true, false>(p);
 }
 
 template <typename E>

@@ -29,6 +29,11 @@
 //     times a zero Q is NaN when the LDS word happens to be NaN / inf), and staging writes only chunks below d_head;
 //   - the fp32 split "half h takes d in [h DHP / 2, (h + 1) DHP / 2)" is the same for Q and K;
 //   - z is stored only for d < d_head: d_head % 8 == 0 keeps every 4-wide register group wholly inside or wholly outside.
+// CAUSAL = true (attn_causal_kernel, attention_causal.hip: the text tower): the reference's additive mask, -inf where key > query, is
+// added to the rounded scores in BOTH passes before anything reads them, so hook_attn_scores holds the masked value, the online max /
+// sum see it, and the pattern above the diagonal is exp(-inf) = exactly 0 in the tap and in the P V operand.  Every row keeps its
+// diagonal, so a good row's max is finite; tiles wholly above a wave's queries are still multiplied (a NaN there must reach the row).
+// The flag is compile-time only: the two non-causal kernels compile to what they compiled to without it.
 // LDS: K 2 x 32 x (DHP EB + 16), V the same (bf16: 2 x DHP x 80), windows 32 KiB:
 //   <float, 32> 50.0 KiB, <bf16, 32> 42.0 KiB, <bf16, 64> 51.0 KiB = three workgroups per CU, <float, 64> 66.0 KiB = two;
 //   <float, 96> 82.0 KiB, <float, 128> 98.0 KiB = one, <bf16, 96> 60.0 KiB, <bf16, 128> 69.0 KiB = two.
@@ -53,7 +58,7 @@ inline ProfScope attn_prof_scope(const AttnParams& p, int elem_bytes, hipStream_
 
 constexpr int ATTN_VT_ROW = 80;             // V^T tile row (bf16): 32 keys x 2 B + 16 pad
 
-template <typename E, int DHP, bool RAGGED>
+template <typename E, int DHP, bool RAGGED, bool CAUSAL>
 __device__ __forceinline__ void attn_stream_body(const AttnParams& p) {
     constexpr int EB = DT<E>::kBytes;
     constexpr bool F32 = EB == 4;
@@ -235,6 +240,15 @@ __device__ __forceinline__ void attn_stream_body(const AttnParams& p) {
         __builtin_amdgcn_wave_barrier();
     };
     auto key_masked = [&](int kt, int e) __attribute__((always_inline)) { return kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * half >= T_; };
+    // CAUSAL: the reference ADDS its mask to the rounded scores (attention.py:262-265 with base_text_transformer.py:188-194: -inf
+    // where key > query, 0 elsewhere).  The add is kept an add: a masked NaN / +inf score becomes NaN, which zeroes its row below
+    auto add_causal_mask = [&](int kt, float (&sc)[16]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int key = kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+            sc[e] = sc[e] + (key > q0 + l31 ? -INFINITY : 0.f);
+        }
+    };
 
     // ---- pass 1: online max / sum (and the score tap)
     unsigned char* sc_dst = p.scores ? reinterpret_cast<unsigned char*>(p.scores) + (int64_t)g * T_ * T_ * EB : nullptr;
@@ -242,6 +256,7 @@ __device__ __forceinline__ void attn_stream_body(const AttnParams& p) {
     auto pass1_tile = [&](int kt) __attribute__((always_inline)) {
         float sc[16];
         score_tile(Kst[kt & 1], sc);
+        if constexpr (CAUSAL) add_causal_mask(kt, sc);
         if (sc_dst) tap_put(kt, sc);
         if (kt + 1 == ntile) {
 #pragma unroll
@@ -298,6 +313,7 @@ __device__ __forceinline__ void attn_stream_body(const AttnParams& p) {
     auto pass2_tile = [&](int kt) __attribute__((always_inline)) {
         float pr[16];
         score_tile(Kst[kt & 1], pr);
+        if constexpr (CAUSAL) add_causal_mask(kt, pr);
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const float x = DT<E>::round(__expf(pr[e] - mrow) * inv_l);       // attention.py:152 pattern.to(cfg.dtype)

@@ -137,6 +137,70 @@ __global__ __launch_bounds__(256) void token_mean_kernel(const T* __restrict__ x
     }
 }
 
+// Token embedding of the text tower (models/base_text_transformer.py:139-145): embed[b][t] = W_E[tokens[b][t]] -- a pure gather,
+// the same bits (hook_embed) -- and full[b][t] = round_T(embed + pos[t]) with the sum in fp32 (hook_full_embed ==
+// blocks.0.hook_resid_pre).  Either output may be NULL.  One wave per token row, 16-byte chunks.  An id outside [0, vocab) reads NO
+// memory: both of its rows are NaN (nn.Embedding device-asserts there; a documented deviation).
+template <typename T>
+__global__ __launch_bounds__(256) void token_embed_kernel(const int64_t* __restrict__ tokens, const T* __restrict__ W_E,
+                                                          const T* __restrict__ pos, T* __restrict__ embed_out,
+                                                          T* __restrict__ full_out, int rows, int Tn, int d, int vocab) {
+    constexpr int PER = DT<T>::kPerChunk;
+    constexpr uint32_t NANW = sizeof(T) == 4 ? 0x7fc00000u : 0x7fc07fc0u;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int64_t id = tokens[row];
+    const bool ok = id >= 0 && id < (int64_t)vocab;
+    const int t = row % Tn;
+    for (int ch = lane; ch < d / PER; ch += 64) {
+        const uint4 e = ok ? *reinterpret_cast<const uint4*>(W_E + id * d + ch * PER) : make_uint4(NANW, NANW, NANW, NANW);
+        if (embed_out) *reinterpret_cast<uint4*>(embed_out + (int64_t)row * d + ch * PER) = e;
+        if (full_out) {
+            const uint4 q = *reinterpret_cast<const uint4*>(pos + (int64_t)t * d + ch * PER);
+            const uint32_t ew[4] = {e.x, e.y, e.z, e.w}, qw[4] = {q.x, q.y, q.z, q.w};
+            uint32_t o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if constexpr (sizeof(T) == 4) {
+                    o[j] = __float_as_uint(__uint_as_float(ew[j]) + __uint_as_float(qw[j]));
+                } else {
+                    o[j] = pack_bf16x2(__uint_as_float(ew[j] << 16) + __uint_as_float(qw[j] << 16),
+                                       __uint_as_float(ew[j] & 0xffff0000u) + __uint_as_float(qw[j] & 0xffff0000u));
+                }
+            }
+            *reinterpret_cast<uint4*>(full_out + (int64_t)row * d + ch * PER) = make_uint4(o[0], o[1], o[2], o[3]);
+        }
+    }
+}
+
+// EOT pooling of the text tower (base_text_transformer.py:151: x[arange(B), tokens.argmax(dim=-1)]): out[b] = x[b][t*], t* the FIRST
+// index of the largest token id of image b (torch.argmax returns the first).  One wave per image: lanes scan the ids, the (id, index)
+// pairs meet in a butterfly (larger id wins, the smaller index on a tie), then the row leaves as 16-byte chunks.
+template <typename T>
+__global__ __launch_bounds__(256) void eot_rows_kernel(const int64_t* __restrict__ tokens, const T* __restrict__ x, T* __restrict__ out,
+                                                       int B, int Tn, int d) {
+    constexpr int PER = DT<T>::kPerChunk;
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    long long best = tokens[(int64_t)b * Tn];
+    int at = 0;
+    for (int t = lane; t < Tn; t += 64) {
+        const long long id = tokens[(int64_t)b * Tn + t];
+        if (id > best || (id == best && t < at)) { best = id; at = t; }
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        const long long ob = __shfl_xor(best, off, 64);
+        const int oa = __shfl_xor(at, off, 64);
+        if (ob > best || (ob == best && oa < at)) { best = ob; at = oa; }
+    }
+    const T* src = x + ((int64_t)b * Tn + at) * d;
+    for (int ch = lane; ch < d / PER; ch += 64)
+        *reinterpret_cast<uint4*>(out + (int64_t)b * d + ch * PER) = *reinterpret_cast<const uint4*>(src + ch * PER);
+}
+
 // out[b][c][r] = in[b][r][c]; 32 x 32 tiles through LDS (+1 pad), coalesced on both sides
 template <typename E>
 __global__ __launch_bounds__(256) void transpose_kernel(const E* __restrict__ in, E* __restrict__ out, int R, int C) {
@@ -204,6 +268,43 @@ int pv_launch_token_mean(int dtype, const void* x, void* out, int B, int T, int 
         else hipLaunchKernelGGL((token_mean_kernel<float, false>), grid, block, 0, stream, (const float*)x, (float*)out, T, d, t0);
     }
     PV_LAUNCH_CHECK("token_mean_kernel");
+    return PV_OK;
+}
+
+int pv_launch_token_embed(int dtype, const int64_t* tokens, const void* W_E, const void* pos, void* embed_out, void* full_out, int B,
+                          int T, int d, int vocab, hipStream_t stream) {
+    PV_REQUIRE(tokens && W_E && pos && B > 0 && T > 0 && vocab > 0 && (embed_out || full_out), "token embed: operands");
+    PV_REQUIRE(d > 0 && d % 8 == 0, "token embed: d_model must be a multiple of 8");
+    PV_REQUIRE(pv_aligned16(W_E) && pv_aligned16(pos) && pv_aligned16(embed_out) && pv_aligned16(full_out) &&
+                   (reinterpret_cast<uintptr_t>(tokens) & 7u) == 0,
+               "token embed: 16-byte aligned tables and outputs, 8-byte aligned ids");
+    PV_REQUIRE((int64_t)B * T < (1ll << 31), "token embed: rows");
+    const int rows = B * T;
+    const dim3 grid((rows + 3) / 4), block(256);
+    const double eb = dtype == PV_DTYPE_BF16 ? 2.0 : 4.0, rd = (double)rows * d;
+    ProfScope prof(PV_PROF_LN, stream, full_out ? rd : 0.0,
+                   rd * eb * (1.0 + (embed_out ? 1.0 : 0.0) + (full_out ? 2.0 : 0.0)) + 8.0 * rows);
+    if (dtype == PV_DTYPE_BF16)
+        hipLaunchKernelGGL((token_embed_kernel<bf16_t>), grid, block, 0, stream, tokens, (const bf16_t*)W_E, (const bf16_t*)pos,
+                           (bf16_t*)embed_out, (bf16_t*)full_out, rows, T, d, vocab);
+    else
+        hipLaunchKernelGGL((token_embed_kernel<float>), grid, block, 0, stream, tokens, (const float*)W_E, (const float*)pos,
+                           (float*)embed_out, (float*)full_out, rows, T, d, vocab);
+    PV_LAUNCH_CHECK("token_embed_kernel");
+    return PV_OK;
+}
+
+int pv_launch_eot_rows(int dtype, const int64_t* tokens, const void* x, void* out, int B, int T, int d, hipStream_t stream) {
+    PV_REQUIRE(tokens && x && out && B > 0 && T > 0, "eot rows: operands");
+    PV_REQUIRE(d > 0 && d % 8 == 0 && pv_aligned16(x) && pv_aligned16(out), "eot rows: d_model % 8 == 0, 16-byte aligned rows");
+    const dim3 grid((B + 3) / 4), block(256);
+    const double eb = dtype == PV_DTYPE_BF16 ? 2.0 : 4.0;
+    ProfScope prof(PV_PROF_LN, stream, 0.0, 2.0 * B * d * eb + 8.0 * B * T);
+    if (dtype == PV_DTYPE_BF16)
+        hipLaunchKernelGGL((eot_rows_kernel<bf16_t>), grid, block, 0, stream, tokens, (const bf16_t*)x, (bf16_t*)out, B, T, d);
+    else
+        hipLaunchKernelGGL((eot_rows_kernel<float>), grid, block, 0, stream, tokens, (const float*)x, (float*)out, B, T, d);
+    PV_LAUNCH_CHECK("eot_rows_kernel");
     return PV_OK;
 }
 

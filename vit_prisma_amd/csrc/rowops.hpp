@@ -29,6 +29,13 @@ int pv_launch_l2norm(int dtype, const void* x, void* out, int rows, int n, hipSt
 // x [B][T][d] (the ln_final output) -> mean over tokens t0 .. T - 1, fp32 accumulation, one rounding (models/base_vit.py:195-208):
 // pair == 0: out [B][d] ("gaap" with t0 = 0); pair == 1: out [B][d][2] = (x[b][0][c], mean) -- the dino-vitb output (t0 = 1)
 int pv_launch_token_mean(int dtype, const void* x, void* out, int B, int T, int d, int t0, int pair, hipStream_t stream);
+// The text tower's embedding (models/base_text_transformer.py:139-145): tokens [B][T] int64, W_E [vocab][d], pos [T][d] ->
+// embed_out [B][T][d] = W_E[tokens] (bit-exact gather) and full_out = round_T(embed + pos); either may be NULL.  An id outside
+// [0, vocab) reads no memory: its rows are NaN.
+int pv_launch_token_embed(int dtype, const int64_t* tokens, const void* W_E, const void* pos, void* embed_out, void* full_out, int B,
+                          int T, int d, int vocab, hipStream_t stream);
+// out [B][d] = x[b][first argmax_t tokens[b][t]] (base_text_transformer.py:151); x [B][T][d]
+int pv_launch_eot_rows(int dtype, const int64_t* tokens, const void* x, void* out, int B, int T, int d, hipStream_t stream);
 int pv_launch_transpose(int elem_bytes, const void* in, void* out, int batch, int R, int C, hipStream_t stream);
 // bf16 NCHW images -> [B*G*G][Kp] patch rows (im2col once per batch, zero-padded to Kp columns), and the matching row padding
 // of the [d][K] patch-embedding weights: the operands of the tiled GEMM for patch sizes its in-kernel gather does not cover

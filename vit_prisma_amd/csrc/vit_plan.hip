@@ -41,9 +41,34 @@ struct pv_vit_plan {
     int Kp;
     unsigned char* conv_wp;
     bool weights_set;
+    // a text plan (pv_text_plan_create): d holds the shared fields (n_tokens = context_length, PV_POOL_CLS stands for the EOT row),
+    // P == T sizes the hook_embed buffer, and the embedding tables replace the patch weights
+    bool is_text;
+    int vocab, causal;
+    const void *token_embed, *pos_embed;
 };
 
 static size_t seg(size_t elems, int eb) { return (size_t)pv_align_up((int64_t)elems * eb, 256); }
+
+static pv_vit_plan* new_plan(const pv_vit_desc& d, int G, int P) {
+    pv_vit_plan* p = new pv_vit_plan();
+    p->d = d;
+    p->G = G;
+    p->P = P;
+    p->T = d.n_tokens;
+    p->HD = d.n_heads * d.d_head;
+    p->EB = d.dtype == PV_DTYPE_BF16 ? 2 : 4;
+    p->WhT = nullptr;
+    p->conv_wp = nullptr;
+    p->Kp = 0;
+    p->patch_prepack = false;
+    p->weights_set = false;
+    p->is_text = false;
+    p->vocab = 0;
+    p->causal = 0;
+    p->token_embed = p->pos_embed = nullptr;
+    return p;
+}
 
 extern "C" int pv_vit_plan_create(const pv_vit_desc* desc, pv_vit_plan** out_plan) {
     PV_REQUIRE(desc && out_plan, "null argument");
@@ -62,18 +87,33 @@ extern "C" int pv_vit_plan_create(const pv_vit_desc* desc, pv_vit_plan** out_pla
     PV_REQUIRE(d.pooling != PV_POOL_CLS_MEAN || (!d.has_head && d.n_tokens >= 2), "PV_POOL_CLS_MEAN needs has_head == 0 and a patch token");
     PV_REQUIRE(d.activation >= PV_ACT_GELU && d.activation <= PV_ACT_RELU, "activation");
     if (d.has_head) PV_REQUIRE(d.n_classes > 0, "n_classes");
-    pv_vit_plan* p = new pv_vit_plan();
-    p->d = d;
-    p->G = G;
-    p->P = P;
-    p->T = d.n_tokens;
-    p->HD = d.n_heads * d.d_head;
-    p->EB = d.dtype == PV_DTYPE_BF16 ? 2 : 4;
-    p->WhT = nullptr;
-    p->conv_wp = nullptr;
+    pv_vit_plan* p = new_plan(d, G, P);
     p->Kp = (d.n_channels * d.patch_size * d.patch_size + 7) / 8 * 8;
     p->patch_prepack = d.dtype == PV_DTYPE_BF16 && d.patch_size != 32 && d.patch_size % 2 == 0 && d.image_size % 2 == 0;
-    p->weights_set = false;
+    *out_plan = p;
+    return PV_OK;
+}
+
+extern "C" int pv_text_plan_create(const pv_text_desc* desc, pv_vit_plan** out_plan) {
+    PV_REQUIRE(desc && out_plan, "null argument");
+    const pv_text_desc& t = *desc;
+    PV_REQUIRE(t.dtype == PV_DTYPE_F32 || t.dtype == PV_DTYPE_BF16, "dtype must be fp32 or bf16");
+    PV_REQUIRE(t.n_layers >= 0 && t.d_model > 0 && t.n_heads > 0 && t.d_head > 0 && t.d_mlp > 0 && t.vocab_size > 0, "dims");
+    PV_REQUIRE(t.d_model % 8 == 0 && t.d_model <= 2048, "d_model must be a multiple of 8 and <= 2048");
+    PV_REQUIRE(t.d_mlp % 8 == 0, "d_mlp must be a multiple of 8");
+    PV_REQUIRE(t.context_length >= 1 && t.context_length <= PV_ATTN_MAX_TOKENS, "context_length must be in [1, " PV_STR(PV_ATTN_MAX_TOKENS) "]");
+    if (t.causal) PV_REQUIRE(t.d_head == 32 || t.d_head == 64, "causal attention needs d_head in {32, 64} (the wide heads have no causal kernel)");
+    else PV_REQUIRE(pv_attention_supported(t.context_length, t.d_head), "attention shape unsupported (T <= " PV_STR(PV_ATTN_MAX_TOKENS) ", d_head in {32, 64} or 64 < d_head <= 128 with d_head % 8 == 0)");
+    PV_REQUIRE(t.activation >= PV_ACT_GELU && t.activation <= PV_ACT_RELU, "activation");
+    if (t.has_head) PV_REQUIRE(t.n_classes > 0, "n_classes");
+    pv_vit_desc d = {};
+    d.n_layers = t.n_layers; d.d_model = t.d_model; d.n_heads = t.n_heads; d.d_head = t.d_head; d.d_mlp = t.d_mlp;
+    d.n_tokens = t.context_length; d.n_classes = t.n_classes; d.has_head = t.has_head; d.normalize_output = t.normalize_output;
+    d.activation = t.activation; d.dtype = t.dtype; d.eps = t.eps; d.attn_scale = t.attn_scale; d.pooling = PV_POOL_CLS;
+    pv_vit_plan* p = new_plan(d, 0, t.context_length);
+    p->is_text = true;
+    p->vocab = t.vocab_size;
+    p->causal = t.causal ? 1 : 0;
     *out_plan = p;
     return PV_OK;
 }
@@ -91,23 +131,13 @@ extern "C" size_t pv_vit_shadow_bytes(const pv_vit_plan* p) {
     return total + 256;
 }
 
-extern "C" int pv_vit_plan_set_weights(pv_vit_plan* p, const pv_vit_weights* w, void* shadow,
-                                       size_t shadow_bytes, void* stream_) {
-    PV_REQUIRE(p && w && shadow, "null argument");
-    PV_REQUIRE(shadow_bytes >= pv_vit_shadow_bytes(p), "shadow buffer too small");
-    PV_REQUIRE(((uintptr_t)shadow & 255) == 0, "shadow buffer must be 256-byte aligned");
-    hipStream_t stream = (hipStream_t)stream_;
+// the shadows both kinds of plan share: per layer Wqkv, WoT, WinT, WoutT, then the head's; `cur` is left behind the last one
+static int pack_block_and_head_shadows(pv_vit_plan* p, const pv_vit_layer_weights* layers, const void* W_H, unsigned char*& cur,
+                                       hipStream_t stream) {
     const pv_vit_desc& d = p->d;
-    PV_REQUIRE(w->conv_w && w->conv_b && w->W_pos && w->ln_final_w && w->ln_final_b, "missing global weights");
-    if (d.use_cls_token) PV_REQUIRE(w->cls_token, "missing cls_token");
-    if (d.layer_norm_pre) PV_REQUIRE(w->ln_pre_w && w->ln_pre_b, "missing ln_pre weights");
-    if (d.has_head) PV_REQUIRE(w->W_H && w->b_H, "missing head weights");
-    PV_REQUIRE(d.n_layers == 0 || w->layers, "missing layer weights");
-    p->w = *w;
-    p->lw.assign(w->layers, w->layers + d.n_layers);
+    p->lw.assign(layers, layers + d.n_layers);
     p->w.layers = p->lw.data();
     p->sh.resize(d.n_layers);
-    unsigned char* cur = (unsigned char*)shadow;
     const int EB = p->EB, HD = p->HD, dm = d.d_model, dmlp = d.d_mlp, H = d.n_heads, dh = d.d_head;
     for (int l = 0; l < d.n_layers; ++l) {
         const pv_vit_layer_weights& L = p->lw[l];
@@ -133,7 +163,51 @@ extern "C" int pv_vit_plan_set_weights(pv_vit_plan* p, const pv_vit_weights* w, 
         p->WhT = cur;
         cur += seg((size_t)d.n_classes * dm, EB);
         int rc;
-        if ((rc = pv_launch_transpose(EB, w->W_H, p->WhT, 1, dm, d.n_classes, stream))) return rc;
+        if ((rc = pv_launch_transpose(EB, W_H, p->WhT, 1, dm, d.n_classes, stream))) return rc;
+    }
+    return PV_OK;
+}
+
+extern "C" int pv_text_plan_set_weights(pv_vit_plan* p, const pv_text_weights* w, void* shadow, size_t shadow_bytes, void* stream_) {
+    PV_REQUIRE(p && w && shadow, "null argument");
+    PV_REQUIRE(p->is_text, "pv_text_plan_set_weights needs a plan of pv_text_plan_create");
+    PV_REQUIRE(shadow_bytes >= pv_vit_shadow_bytes(p), "shadow buffer too small");
+    PV_REQUIRE(((uintptr_t)shadow & 255) == 0, "shadow buffer must be 256-byte aligned");
+    const pv_vit_desc& d = p->d;
+    PV_REQUIRE(w->token_embed && w->pos_embed && w->ln_final_w && w->ln_final_b, "missing global weights");
+    PV_REQUIRE(pv_aligned16(w->token_embed) && pv_aligned16(w->pos_embed), "token_embed / pos_embed must be 16-byte aligned");
+    if (d.has_head) PV_REQUIRE(w->W_H && w->b_H, "missing head weights");
+    PV_REQUIRE(d.n_layers == 0 || w->layers, "missing layer weights");
+    p->w = pv_vit_weights{};
+    p->w.ln_final_w = w->ln_final_w; p->w.ln_final_b = w->ln_final_b; p->w.W_H = w->W_H; p->w.b_H = w->b_H;
+    p->token_embed = w->token_embed;
+    p->pos_embed = w->pos_embed;
+    unsigned char* cur = (unsigned char*)shadow;
+    int rc;
+    if ((rc = pack_block_and_head_shadows(p, w->layers, w->W_H, cur, (hipStream_t)stream_))) return rc;
+    p->weights_set = true;
+    return PV_OK;
+}
+
+extern "C" int pv_vit_plan_set_weights(pv_vit_plan* p, const pv_vit_weights* w, void* shadow,
+                                       size_t shadow_bytes, void* stream_) {
+    PV_REQUIRE(p && w && shadow, "null argument");
+    PV_REQUIRE(!p->is_text, "a text plan takes its weights through pv_text_plan_set_weights");
+    PV_REQUIRE(shadow_bytes >= pv_vit_shadow_bytes(p), "shadow buffer too small");
+    PV_REQUIRE(((uintptr_t)shadow & 255) == 0, "shadow buffer must be 256-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    const pv_vit_desc& d = p->d;
+    PV_REQUIRE(w->conv_w && w->conv_b && w->W_pos && w->ln_final_w && w->ln_final_b, "missing global weights");
+    if (d.use_cls_token) PV_REQUIRE(w->cls_token, "missing cls_token");
+    if (d.layer_norm_pre) PV_REQUIRE(w->ln_pre_w && w->ln_pre_b, "missing ln_pre weights");
+    if (d.has_head) PV_REQUIRE(w->W_H && w->b_H, "missing head weights");
+    PV_REQUIRE(d.n_layers == 0 || w->layers, "missing layer weights");
+    p->w = *w;
+    unsigned char* cur = (unsigned char*)shadow;
+    const int EB = p->EB, dm = d.d_model;
+    {
+        int rc;
+        if ((rc = pack_block_and_head_shadows(p, w->layers, w->W_H, cur, stream))) return rc;
     }
     if (p->patch_prepack) {
         const int K = d.n_channels * d.patch_size * d.patch_size;
@@ -188,7 +262,7 @@ extern "C" size_t pv_vit_workspace_bytes(const pv_vit_plan* p, int32_t batch) {
 
 namespace {
 // entry_stage / exit_stage: PV_STAGE_* (positions inside a block: entry, ln1, q/k/v ready, scores, pattern, z ready, resid_mid, ln2, mlp pre, mlp post ready)
-int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, const void* const* act_in, int32_t B,
+int vit_forward_impl(pv_vit_plan* p, const void* images, const int64_t* tokens, const void* resid_in, const void* const* act_in, int32_t B,
                      int32_t first_block, int32_t entry_stage, int32_t n_blocks, int32_t exit_stage, int32_t run_head,
                      const pv_tap* taps, int32_t n_taps, void* workspace, size_t workspace_bytes, void* out, void* stream_);
 }  // namespace
@@ -197,7 +271,7 @@ extern "C" int pv_vit_forward(pv_vit_plan* p, const void* images, int32_t B, int
                               int32_t run_head, const pv_tap* taps, int32_t n_taps, void* workspace,
                               size_t workspace_bytes, void* out, void* stream_) {
     PV_REQUIRE(images, "null argument");
-    return vit_forward_impl(p, images, nullptr, nullptr, B, 0, 0, n_blocks, 0, run_head, taps, n_taps, workspace, workspace_bytes, out, stream_);
+    return vit_forward_impl(p, images, nullptr, nullptr, nullptr, B, 0, 0, n_blocks, 0, run_head, taps, n_taps, workspace, workspace_bytes, out, stream_);
 }
 
 extern "C" int pv_vit_forward_seg(pv_vit_plan* p, const void* images, const void* resid_in, int32_t B, int32_t first_block,
@@ -210,7 +284,7 @@ extern "C" int pv_vit_forward_seg(pv_vit_plan* p, const void* images, const void
     PV_REQUIRE(!entry_mid || first_block < p->d.n_layers, "entry_mid needs a block to resume");
     PV_REQUIRE(!exit_mid || (end_block < p->d.n_layers && !run_head), "exit_mid stops inside block end_block");
     PV_REQUIRE(!(entry_mid && first_block == end_block && !exit_mid), "a mid-block entry must finish its block");
-    return vit_forward_impl(p, images, resid_in, nullptr, B, first_block, entry_mid ? PV_STAGE_MID : 0, end_block,
+    return vit_forward_impl(p, images, nullptr, resid_in, nullptr, B, first_block, entry_mid ? PV_STAGE_MID : 0, end_block,
                             exit_mid ? PV_STAGE_MID : 0, run_head, taps, n_taps, workspace, workspace_bytes, out, stream_);
 }
 
@@ -234,7 +308,7 @@ extern "C" int pv_vit_forward_stage(pv_vit_plan* p, const void* images, const vo
     if (entry_stage == PV_STAGE_SCORES || entry_stage == PV_STAGE_PATTERN) PV_REQUIRE(act_in0 && act_in1, "entry at PV_STAGE_SCORES / PV_STAGE_PATTERN needs the activation and v");
     const void* act[3] = {act_in0, act_in1, act_in2};
     for (int i = 0; i < 3; ++i) PV_REQUIRE(!act[i] || pv_aligned16(act[i]), "activation inputs must be 16-byte aligned");
-    return vit_forward_impl(p, images, resid_in, act, B, first_block, entry_stage, end_block, exit_stage, run_head, taps, n_taps,
+    return vit_forward_impl(p, images, nullptr, resid_in, act, B, first_block, entry_stage, end_block, exit_stage, run_head, taps, n_taps,
                             workspace, workspace_bytes, out, stream_);
 }
 
@@ -243,14 +317,16 @@ extern "C" int pv_vit_forward_from(pv_vit_plan* p, const void* resid_in, int32_t
                                    size_t workspace_bytes, void* out, void* stream_) {
     PV_REQUIRE(resid_in && pv_aligned16(resid_in), "resid_in must be a 16-byte aligned device pointer");
     PV_REQUIRE(p && first_block >= 0 && first_block <= p->d.n_layers && first_block <= n_blocks, "first_block out of range");
-    return vit_forward_impl(p, nullptr, resid_in, nullptr, B, first_block, 0, n_blocks, 0, run_head, taps, n_taps, workspace, workspace_bytes, out, stream_);
+    return vit_forward_impl(p, nullptr, nullptr, resid_in, nullptr, B, first_block, 0, n_blocks, 0, run_head, taps, n_taps, workspace, workspace_bytes, out, stream_);
 }
 
 namespace {
-int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, const void* const* act_in, int32_t B,
+int vit_forward_impl(pv_vit_plan* p, const void* images, const int64_t* tokens, const void* resid_in, const void* const* act_in, int32_t B,
                      int32_t first_block, int32_t entry_stage, int32_t n_blocks, int32_t exit_stage, int32_t run_head,
                      const pv_tap* taps, int32_t n_taps, void* workspace, size_t workspace_bytes, void* out, void* stream_) {
-    PV_REQUIRE(p && (images || resid_in) && workspace, "null argument");
+    PV_REQUIRE(p && (images || tokens || resid_in) && workspace, "null argument");
+    // tokens: only pv_text_forward passes them, and only for a text plan -- refused here, before any launch
+    PV_REQUIRE(p->is_text == (tokens != nullptr), "a text plan runs through pv_text_forward, a vision plan through pv_vit_forward*");
     PV_REQUIRE(p->weights_set, "pv_vit_plan_set_weights has not been called");
     PV_REQUIRE(B > 0, "batch must be positive");
     const pv_vit_desc& d = p->d;
@@ -281,6 +357,10 @@ int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, c
                            t.slot != PV_SLOT_LN1_NORM_F32 && t.slot != PV_SLOT_LN2_NORM_F32,
                        "*_NORM_F32 slots exist only in bf16 mode");
         }
+        if (p->is_text) {
+            PV_REQUIRE(t.slot != PV_SLOT_LNPRE_SCALE && t.slot != PV_SLOT_LNPRE_NORM_F32 && t.slot != PV_SLOT_LNPRE_OUT,
+                       "a text plan has no PV_SLOT_LNPRE_* slots: ln_pre never runs (base_text_transformer.py:139-146)");
+        }
         tap_at(t.slot, layer) = t.dst;
     }
     auto pick = [&](int slot, int layer, size_t ws_off) -> void* {
@@ -294,6 +374,11 @@ int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, c
         // resumed forward (pv_vit_forward_from): the caller hands in the residual stream entering `first_block`
         // (the value a Python hook at a block boundary returned); the embedding stages are skipped
         resid = const_cast<void*>(resid_in);
+    } else if (p->is_text) {
+        // ---- token + position embedding (base_text_transformer.py:125-143): hook_embed is the gather itself, hook_full_embed the
+        // residual stream entering block 0
+        resid = pick(PV_SLOT_FULL_EMBED, 0, ws.resid_a);
+        if ((rc = pv_launch_token_embed(dt, tokens, p->token_embed, p->pos_embed, tap_at(PV_SLOT_EMBED, 0), resid, B, T, dm, p->vocab, stream))) return rc;
     } else {
     // ---- patch embedding: stride-p conv as an im2col-free GEMM (patch_embedding.py:26-32)
     void* embed = pick(PV_SLOT_EMBED, 0, ws.embed);
@@ -397,7 +482,7 @@ int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, c
             AttnParams a = {};
             a.q = q; a.k = k; a.v = v; a.z = z;
             a.scores = tap_at(PV_SLOT_SCORES, l); a.pattern = tap_at(PV_SLOT_PATTERN, l);
-            a.B = B; a.T = T; a.H = d.n_heads; a.dh = d.d_head; a.attn_scale = d.attn_scale;
+            a.B = B; a.T = T; a.H = d.n_heads; a.dh = d.d_head; a.attn_scale = d.attn_scale; a.causal = p->causal;
             if ((rc = pv_launch_attention(dt, a, stream))) return rc;
         }
         } else if (es == PV_STAGE_SCORES || es == PV_STAGE_PATTERN) {
@@ -490,6 +575,7 @@ int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, c
     if (!run_head) return PV_OK;
 
     // ---- ln_final on all tokens only if one of its taps is requested or the pooling reads them all, else on the CLS rows only
+    // (a text plan: on the EOT rows only)
     const bool lnf_all = d.pooling != PV_POOL_CLS || tap_at(PV_SLOT_LNF_SCALE, 0) || tap_at(PV_SLOT_LNF_NORM_F32, 0) || tap_at(PV_SLOT_LNF_OUT, 0);
     void* lnf = pick(PV_SLOT_LNF_OUT, 0, ws.lnf);
     int64_t lnf_ld;   // row stride (elements) between CLS rows of consecutive images
@@ -501,6 +587,12 @@ int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, c
             L.scale_out = (float*)tap_at(PV_SLOT_LNF_SCALE, 0);
             L.norm_f32_out = (float*)tap_at(PV_SLOT_LNF_NORM_F32, 0);
             lnf_ld = (int64_t)T * dm;
+        } else if (p->is_text) {
+            // the residual rows at the EOT tokens first (base_text_transformer.py:151), LayerNorm on those B rows
+            void* rows = wsb + ws.pooled;
+            if ((rc = pv_launch_eot_rows(dt, tokens, resid, rows, B, T, dm, stream))) return rc;
+            L.x = rows; L.ldx = dm; L.rows = B;
+            lnf_ld = dm;
         } else {
             L.ldx = (int64_t)T * dm; L.rows = B;
             lnf_ld = dm;
@@ -513,6 +605,13 @@ int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, c
     const int nout = d.has_head ? d.n_classes : (cls_mean ? 2 * dm : dm);
     void* head_tap = tap_at(PV_SLOT_HEAD_OUT, 0);
     void* hb = head_tap ? head_tap : (d.normalize_output ? (void*)(wsb + ws.head) : out);
+    if (p->is_text && lnf_all) {
+        // x[arange(B), tokens.argmax(dim=-1)] of the ln_final output (base_text_transformer.py:151)
+        void* pooled = wsb + ws.pooled;
+        if ((rc = pv_launch_eot_rows(dt, tokens, lnf, pooled, B, T, dm, stream))) return rc;
+        lnf = pooled;
+        lnf_ld = dm;
+    }
     if (d.pooling != PV_POOL_CLS) {
         // "gaap": the mean over all tokens feeds the head (or IS the output); dino-vitb: [B, d, 2] = (cls, mean over the patches)
         void* pooled = (d.has_head) ? (void*)(wsb + ws.pooled) : hb;
@@ -539,7 +638,23 @@ int vit_forward_impl(pv_vit_plan* p, const void* images, const void* resid_in, c
 }
 }  // namespace
 
+extern "C" int pv_text_forward(pv_vit_plan* p, const int64_t* tokens, int32_t B, int32_t run_head, const pv_tap* taps, int32_t n_taps,
+                               void* workspace, size_t workspace_bytes, void* out, void* stream_) {
+    PV_REQUIRE(p && tokens, "null argument");
+    PV_REQUIRE(p->is_text, "pv_text_forward needs a plan of pv_text_plan_create (a vision plan runs through pv_vit_forward*)");
+    return vit_forward_impl(p, nullptr, tokens, nullptr, nullptr, B, 0, 0, p->d.n_layers, 0, run_head, taps, n_taps, workspace,
+                            workspace_bytes, out, stream_);
+}
+
 // ---- kernel-level entry points -------------------------------------------------------------
+extern "C" int pv_attention(int32_t dtype, const void* q, const void* k, const void* v, int32_t B, int32_t T, int32_t H, int32_t dh,
+                            float attn_scale, int32_t causal, void* scores, void* pattern, void* z, void* stream) {
+    PV_REQUIRE(B > 0 && T > 0 && H > 0 && dh > 0, "pv_attention: dims");
+    AttnParams a = {};
+    a.q = q; a.k = k; a.v = v; a.z = z; a.scores = scores; a.pattern = pattern;
+    a.B = B; a.T = T; a.H = H; a.dh = dh; a.attn_scale = attn_scale; a.causal = causal ? 1 : 0;
+    return pv_launch_attention(dtype, a, (hipStream_t)stream);
+}
 extern "C" int pv_gemm_bias(int32_t dtype, const void* A, int64_t lda, const void* Bt, int64_t ldb,
                             const void* bias, void* C, int64_t ldc, int32_t M, int32_t N, int32_t K,
                             void* stream) {

@@ -17,7 +17,7 @@ from typing import Any, Optional, Type
 
 import torch
 
-from .configs import HookedViTConfig
+from .configs import HookedTextTransformerConfig, HookedViTConfig
 from .synth import ARCHS
 from .vit import HookedViT
 from .weights import load_clip_vision_weights, load_dino_weights
@@ -54,6 +54,28 @@ WIDE_ARCH = {
     "open-clip:laion/CLIP-ViT-g-14-laion2B-s34B-b88K": "clip-vit-g14",
     "open-clip:laion/CLIP-ViT-bigG-14-laion2B-39B-b160k": "clip-vit-bigg14",
 }
+# the text towers of the reference's registry (OPEN_CLIP_TEXT_CONFIGS, models/model_config_registry.py:605-674): every one d_head 64
+# at context 77.  The fields are the registry's, pinned by tests/golden/model_registry_text.json (tests/golden/gen_golden_text.py);
+# served by load_text_config / list_available_text_models, NOT by load_config / list_available_models (whose values stay as they are).
+BASE_TEXT_CONFIG = dict(d_model=768, n_heads=12, n_layers=12, d_mlp=3072, d_head=64, vocab_size=49408, context_length=77, eps=1e-5,
+                        normalization_type="LN", layer_norm_pre=True)
+_XLM_LARGE = dict(d_model=1024, n_heads=16, n_layers=24, d_mlp=4096, vocab_size=250002)
+TEXT_CONFIGS = {
+    "open-clip:laion/CLIP-ViT-B-32-DataComp.XL-s13B-b90K": {},
+    "open-clip:laion/CLIP-ViT-L-14-DataComp.XL-s13B-b90K": {},
+    "open-clip:laion/CLIP-ViT-B-32-xlm-roberta-base-laion5B-s13B-b90k": {"vocab_size": 250002},
+    "open-clip:laion/CLIP-ViT-B-32-roberta-base-laion2B-s12B-b32k": {"vocab_size": 50265},
+    "open-clip:laion/CLIP-ViT-H-14-frozen-xlm-roberta-large-laion5B-s13B-b90k": _XLM_LARGE,
+    "open-clip:laion/CLIP-ViT-B-16-CommonPool.L-s1B-b8K": {},
+    "open-clip:laion/CLIP-ViT-B-16-CommonPool.L.basic-s1B-b8K": {},
+    "open-clip:laion/CLIP-ViT-B-16-CommonPool.L.clip-s1B-b8K": {},
+    "open-clip:laion/CLIP-ViT-B-16-CommonPool.L.laion-s1B-b8K": {},
+    "open-clip:laion/CLIP-ViT-B-32-CommonPool.M-s128M-b4K": {},
+    "open-clip:laion/CLIP-ViT-B-32-CommonPool.S-s13M-b4K": {},
+    "open-clip:laion/CLIP-ViT-L-14-CommonPool.XL-s13B-b90K": {},
+    "open-clip:laion/CoCa-ViT-B-32-laion2B-s13B-b90k": {},
+    "open-clip:laion/CoCa-ViT-L-14-laion2B-s13B-b90k": {},
+}
 DTYPE_FROM_STRING = {"float32": torch.float32, "fp32": torch.float32, "float16": torch.float16, "fp16": torch.float16,
                      "bfloat16": torch.bfloat16, "bf16": torch.bfloat16}
 
@@ -72,6 +94,20 @@ def load_config(model_name: str, dtype: torch.dtype = torch.float32, device: str
     return HookedViTConfig(**kw, dtype=dtype, device=device)
 
 
+def list_available_text_models():
+    return sorted(TEXT_CONFIGS)
+
+
+def load_text_config(model_name: str, dtype: torch.dtype = torch.float32, device: str = "cuda", **overrides) -> HookedTextTransformerConfig:
+    """The registry's text config of ``model_name`` (its fields over the dataclass defaults, as the reference's load_config applies
+    them); everything the registry leaves to the checkpoint (n_classes = the joint width, ...) comes in through ``overrides``."""
+    if model_name not in TEXT_CONFIGS:
+        raise ValueError(f"{model_name!r}: no text tower in the registry; known: {list_available_text_models()}")
+    kw = {**BASE_TEXT_CONFIG, **TEXT_CONFIGS[model_name], "model_name": model_name}
+    kw.update(overrides)
+    return HookedTextTransformerConfig(**kw, dtype=dtype, device=device)
+
+
 def load_hooked_model(model_name: str, model_class: Optional[Type] = None, model_type: Any = None, device: str = "cuda",
                       dtype: torch.dtype = torch.float32, pretrained: bool = True, fold_ln: bool = False,
                       center_writing_weights: bool = False, fold_value_biases: bool = True,
@@ -85,7 +121,8 @@ def load_hooked_model(model_name: str, model_class: Optional[Type] = None, model
     if fold_ln or center_writing_weights or refactor_factored_attn_matrices:
         raise NotImplementedError("fold_ln / center_writing_weights / refactor_factored_attn_matrices are not implemented in this build")
     if model_type is not None and str(getattr(model_type, "name", model_type)).upper() not in ("VISION", "MODELTYPE.VISION"):
-        raise NotImplementedError("only the vision tower is built here (SURVEY.md section 8: the text tower is out of scope)")
+        raise NotImplementedError("load_hooked_model builds the vision tower; the text tower is HookedTextTransformer(load_text_config(name, ...)) "
+                                  "with weights from weights.convert_open_clip_text_weights")
     # cfg.dtype is set too: the reference's loader forgets it and its bf16 forward raises -- deliberate fix
     cfg = load_config(model_name, dtype=dtype, device=device)
     model = (model_class or HookedViT)(cfg)

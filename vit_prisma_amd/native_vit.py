@@ -111,19 +111,8 @@ class NativeViT:
         self.device = torch.device(device)
         self.n_tokens = n_tokens
         self.lib = N.lib()
-        desc = N.VitDesc(
-            n_layers=cfg.n_layers, d_model=cfg.d_model, n_heads=cfg.n_heads, d_head=cfg.d_head,
-            d_mlp=cfg.d_mlp, n_channels=cfg.n_channels, patch_size=cfg.patch_size,
-            image_size=cfg.image_size, n_tokens=n_tokens, n_classes=cfg.n_classes,
-            use_cls_token=int(bool(cfg.use_cls_token)), layer_norm_pre=int(bool(cfg.layer_norm_pre)),
-            has_head=int(cfg.return_type != "pre_logits"), normalize_output=int(bool(cfg.normalize_output)),
-            activation=N.PV_ACT[cfg.activation_name],
-            dtype=N.PV_DTYPE_BF16 if cfg.dtype == torch.bfloat16 else N.PV_DTYPE_F32,
-            eps=float(cfg.eps),
-            attn_scale=float(cfg.d_head ** 0.5) if cfg.use_attn_scale else 1.0,
-            pooling=pooling_mode(cfg))
         self._plan = C.c_void_p()
-        N.check(self.lib.pv_vit_plan_create(C.byref(desc), C.byref(self._plan)), "pv_vit_plan_create")
+        self._create_plan()
         self._shadow: Optional[torch.Tensor] = None
         self._weights_key = None
         self._frozen = False
@@ -138,6 +127,21 @@ class NativeViT:
         # slab base the ctypes tap array.  A 214-tap call spent 1.7 ms on the host rebuilding them (a bs = 32 forward takes 0.45 ms)
         self._layouts: Dict[tuple, tuple] = {}
         self._tap_arrays: Dict[tuple, object] = {}
+
+    def _create_plan(self) -> None:
+        cfg = self.cfg
+        desc = N.VitDesc(
+            n_layers=cfg.n_layers, d_model=cfg.d_model, n_heads=cfg.n_heads, d_head=cfg.d_head,
+            d_mlp=cfg.d_mlp, n_channels=cfg.n_channels, patch_size=cfg.patch_size,
+            image_size=cfg.image_size, n_tokens=self.n_tokens, n_classes=cfg.n_classes,
+            use_cls_token=int(bool(cfg.use_cls_token)), layer_norm_pre=int(bool(cfg.layer_norm_pre)),
+            has_head=int(cfg.return_type != "pre_logits"), normalize_output=int(bool(cfg.normalize_output)),
+            activation=N.PV_ACT[cfg.activation_name],
+            dtype=N.PV_DTYPE_BF16 if cfg.dtype == torch.bfloat16 else N.PV_DTYPE_F32,
+            eps=float(cfg.eps),
+            attn_scale=float(cfg.d_head ** 0.5) if cfg.use_attn_scale else 1.0,
+            pooling=pooling_mode(cfg))
+        N.check(self.lib.pv_vit_plan_create(C.byref(desc), C.byref(self._plan)), "pv_vit_plan_create")
 
     def __del__(self):
         try:
@@ -174,9 +178,9 @@ class NativeViT:
             return None  # dropout is the identity in eval mode; training mode is checked by the caller
         return None
 
-    def _collect(self, model) -> Tuple[N.VitWeights, list]:
+    def _borrow(self, keep: List[torch.Tensor]):
+        """P(tensor) -> its device pointer, the (contiguous) tensor kept alive in ``keep``."""
         cfg = self.cfg
-        keep: List[torch.Tensor] = []
 
         def P(t: Optional[torch.Tensor]) -> Optional[int]:
             if t is None:
@@ -188,8 +192,10 @@ class NativeViT:
                 t = t.contiguous()
             keep.append(t)
             return t.data_ptr()
+        return P
 
-        L = (N.VitLayerWeights * max(cfg.n_layers, 1))()
+    def _collect_layers(self, model, P):
+        L = (N.VitLayerWeights * max(self.cfg.n_layers, 1))()
         for i, blk in enumerate(model.blocks):
             a, m = blk.attn, blk.mlp
             L[i] = N.VitLayerWeights(
@@ -197,6 +203,13 @@ class NativeViT:
                 b_Q=P(a.b_Q), b_K=P(a.b_K), b_V=P(a.b_V), W_O=P(a.W_O), b_O=P(a.b_O),
                 ln2_w=P(blk.ln2.w), ln2_b=P(blk.ln2.b), W_in=P(m.W_in), b_in=P(m.b_in),
                 W_out=P(m.W_out), b_out=P(m.b_out))
+        return L
+
+    def _collect(self, model) -> Tuple[N.VitWeights, list]:
+        cfg = self.cfg
+        keep: List[torch.Tensor] = []
+        P = self._borrow(keep)
+        L = self._collect_layers(model, P)
         has_head = cfg.return_type != "pre_logits"
         W = N.VitWeights(
             cls_token=P(model.cls_token) if cfg.use_cls_token else None,
@@ -215,11 +228,7 @@ class NativeViT:
         ``model.parameters()``, a different walk -- tied parameters de-duplicated, spliced modules included -- so after one real
         repack the two could never match again and every forward repacked the whole shadow)."""
         cfg = self.cfg
-        slots = []
-        for blk in model.blocks:
-            slots += [(blk.ln1, "w"), (blk.ln1, "b"), (blk.ln2, "w"), (blk.ln2, "b")]
-            slots += [(blk.attn, n) for n in ("W_Q", "W_K", "W_V", "b_Q", "b_K", "b_V", "W_O", "b_O")]
-            slots += [(blk.mlp, n) for n in ("W_in", "b_in", "W_out", "b_out")]
+        slots = self._block_slots(model)
         if cfg.use_cls_token:
             slots.append((model, "cls_token"))
         slots += [(model.embed.proj, "weight"), (model.embed.proj, "bias"), (model.pos_embed, "W_pos"), (model.ln_final, "w"), (model.ln_final, "b")]
@@ -227,6 +236,15 @@ class NativeViT:
             slots += [(model.ln_pre, "w"), (model.ln_pre, "b")]
         if cfg.return_type != "pre_logits":
             slots += [(model.head, "W_H"), (model.head, "b_H")]
+        return slots
+
+    @staticmethod
+    def _block_slots(model) -> list:
+        slots = []
+        for blk in model.blocks:
+            slots += [(blk.ln1, "w"), (blk.ln1, "b"), (blk.ln2, "w"), (blk.ln2, "b")]
+            slots += [(blk.attn, n) for n in ("W_Q", "W_K", "W_V", "b_Q", "b_K", "b_V", "W_O", "b_O")]
+            slots += [(blk.mlp, n) for n in ("W_in", "b_in", "W_out", "b_out")]
         return slots
 
     @staticmethod
@@ -254,11 +272,14 @@ class NativeViT:
         if self._shadow is None or self._shadow.numel() < nbytes:
             self._shadow = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        N.check(self.lib.pv_vit_plan_set_weights(self._plan, C.byref(W), self._shadow.data_ptr(), nbytes, stream),
-                "pv_vit_plan_set_weights")
+        self._set_weights(W, nbytes, stream)
         self._keepalive = keep
         self._weights_key = key
         self.n_repack += 1
+
+    def _set_weights(self, W, nbytes: int, stream: int) -> None:
+        N.check(self.lib.pv_vit_plan_set_weights(self._plan, C.byref(W), self._shadow.data_ptr(), nbytes, stream),
+                "pv_vit_plan_set_weights")
 
     def freeze_weights(self, frozen: bool = True) -> None:
         self._frozen = frozen
@@ -270,6 +291,27 @@ class NativeViT:
             self._workspace = None
             self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._workspace
+
+    def _check_input(self, images: torch.Tensor) -> torch.Tensor:
+        """The model input as the plan reads it (dtype, layout); raises on a shape the plan was not built for."""
+        cfg = self.cfg
+        if images.dtype != cfg.dtype:
+            images = images.to(cfg.dtype)
+        images = images.contiguous()
+        if tuple(images.shape[1:]) != (cfg.n_channels, cfg.image_size, cfg.image_size):
+            raise ValueError(f"expected images [B,{cfg.n_channels},{cfg.image_size},{cfg.image_size}], got {tuple(images.shape)}")
+        return images
+
+    def _launch_full(self, inp: torch.Tensor, B: int, n_blocks: int, run_head: bool, taps, n_taps: int, ws: torch.Tensor,
+                     out_ptr: Optional[int], stream: int) -> None:
+        """The forward from the model input (no resumed segment)."""
+        N.check(self.lib.pv_vit_forward(self._plan, inp.data_ptr(), B, n_blocks, int(run_head), taps, n_taps,
+                                        ws.data_ptr(), ws.numel(), out_ptr, stream),
+                "pv_vit_forward")
+
+    def _pos_embed_view(self, model, B: int) -> torch.Tensor:
+        """hook_pos_embed: stride-0 broadcast view of W_pos, as in position_embedding.py:36-38"""
+        return model.pos_embed.W_pos.detach().unsqueeze(0).expand(B, -1, -1)
 
     def forward(self, model, images: Optional[torch.Tensor], names: Sequence[str], n_blocks: int, run_head: bool,
                 cache_device=None, remove_batch_dim: bool = False, first_block: int = 0,
@@ -304,12 +346,8 @@ class NativeViT:
         else:
             if images.device != self.device:
                 raise N.NativeError(f"input on {images.device}, model on {self.device}")
-            if images.dtype != cfg.dtype:
-                images = images.to(cfg.dtype)
-            images = images.contiguous()
+            images = self._check_input(images)
             B = images.shape[0]
-            if tuple(images.shape[1:]) != (cfg.n_channels, cfg.image_size, cfg.image_size):
-                raise ValueError(f"expected images [B,{cfg.n_channels},{cfg.image_size},{cfg.image_size}], got {tuple(images.shape)}")
         self.sync_weights(model)
 
         lkey = None if tap_dst else (tuple(names), B, n_blocks, bool(run_head), exit_stage)
@@ -367,7 +405,7 @@ class NativeViT:
         else:
             out_off = total
             if run_head:
-                nbytes = images.element_size()
+                nbytes = _ESIZE[cfg.dtype]
                 for dim in out_shape:
                     nbytes *= dim
                 total += (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
@@ -401,9 +439,7 @@ class NativeViT:
         if last is not None and last[0] != stream:
             cur.wait_event(last[1])
         if resid_in is None and not exit_stage:
-            N.check(self.lib.pv_vit_forward(self._plan, images.data_ptr(), B, n_blocks, int(run_head), taps, n_taps,
-                                            ws.data_ptr(), ws.numel(), (base + out_off) if run_head else None, stream),
-                    "pv_vit_forward")
+            self._launch_full(images, B, n_blocks, run_head, taps, n_taps, ws, (base + out_off) if run_head else None, stream)
         else:
             ap = [a.data_ptr() for a in acts] + [None] * (3 - len(acts))
             N.check(self.lib.pv_vit_forward_stage(self._plan, images.data_ptr() if resid_in is None else None,
@@ -432,8 +468,7 @@ class NativeViT:
         for n in names:
             s = specs[n]
             if s.slot < 0:
-                # hook_pos_embed: stride-0 broadcast view of W_pos, as in position_embedding.py:36-38
-                t = model.pos_embed.W_pos.detach().unsqueeze(0).expand(B, -1, -1)
+                t = self._pos_embed_view(model, B)
                 if cache_device is not None:
                     t = t.to(cache_device)
             elif (s.slot, s.layer) in external:
@@ -452,3 +487,76 @@ class NativeViT:
             off, s = offsets[(specs[out_name].slot, specs[out_name].layer)]
             out = view(slab, off, s.dtype, s.shape)
         return out, cache
+
+
+class NativeText(NativeViT):
+    """Owns one text plan (pv_text_plan_create) for one (config, dtype, device): HookedTextTransformer's forward on the same
+    blocks, arena, weight-change detection and workspace cache as NativeViT; only the plan's ends differ."""
+
+    def __init__(self, cfg, device: torch.device, causal: bool = True):
+        self.causal = bool(causal)
+        super().__init__(cfg, cfg.context_length, device)
+
+    def _create_plan(self) -> None:
+        cfg = self.cfg
+        desc = N.TextDesc(
+            n_layers=cfg.n_layers, d_model=cfg.d_model, n_heads=cfg.n_heads, d_head=cfg.d_head, d_mlp=cfg.d_mlp,
+            context_length=cfg.context_length, vocab_size=cfg.vocab_size, n_classes=cfg.n_classes,
+            has_head=int(cfg.return_type != "pre_logits"), normalize_output=int(bool(cfg.normalize_output)),
+            causal=int(self.causal), activation=N.PV_ACT[cfg.activation_name],
+            dtype=N.PV_DTYPE_BF16 if cfg.dtype == torch.bfloat16 else N.PV_DTYPE_F32, eps=float(cfg.eps),
+            attn_scale=float(cfg.d_head ** 0.5) if cfg.use_attn_scale else 1.0)
+        N.check(self.lib.pv_text_plan_create(C.byref(desc), C.byref(self._plan)), "pv_text_plan_create")
+
+    @staticmethod
+    def supported(cfg) -> Optional[str]:
+        """None if a text plan can be built for this config, else why not (the shape rules themselves are the plan's: its own
+        error text is passed through by the caller)."""
+        if cfg.dtype not in (torch.float32, torch.bfloat16):
+            return f"dtype {cfg.dtype}"
+        if cfg.normalization_type != "LN":
+            return f"normalization_type {cfg.normalization_type}"
+        if cfg.activation_name not in N.PV_ACT:
+            return f"activation {cfg.activation_name}"
+        if cfg.attn_only or cfg.use_bert_block:
+            return "architecture variant"
+        return None
+
+    def _collect(self, model) -> Tuple[N.TextWeights, list]:
+        keep: List[torch.Tensor] = []
+        P = self._borrow(keep)
+        L = self._collect_layers(model, P)
+        has_head = self.cfg.return_type != "pre_logits"
+        W = N.TextWeights(
+            token_embed=P(model.token_embed.weight), pos_embed=P(model.pos_embed),
+            ln_final_w=P(model.ln_final.w), ln_final_b=P(model.ln_final.b),
+            W_H=P(model.head.W_H) if has_head else None, b_H=P(model.head.b_H) if has_head else None,
+            layers=C.cast(L, C.POINTER(N.VitLayerWeights)))
+        return W, [keep, L]
+
+    def _plan_slots(self, model) -> list:
+        slots = self._block_slots(model)
+        slots += [(model.token_embed, "weight"), (model, "pos_embed"), (model.ln_final, "w"), (model.ln_final, "b")]
+        if self.cfg.return_type != "pre_logits":
+            slots += [(model.head, "W_H"), (model.head, "b_H")]
+        return slots
+
+    def _set_weights(self, W, nbytes: int, stream: int) -> None:
+        N.check(self.lib.pv_text_plan_set_weights(self._plan, C.byref(W), self._shadow.data_ptr(), nbytes, stream),
+                "pv_text_plan_set_weights")
+
+    def _check_input(self, tokens: torch.Tensor) -> torch.Tensor:
+        if tokens.ndim != 2 or tokens.shape[1] != self.cfg.context_length:
+            raise ValueError(f"expected tokens [B,{self.cfg.context_length}], got {tuple(tokens.shape)}")
+        return tokens.to(torch.int64).contiguous()          # (int32 ids are widened on the device)
+
+    def _launch_full(self, inp, B, n_blocks, run_head, taps, n_taps, ws, out_ptr, stream) -> None:
+        if n_blocks != self.cfg.n_layers:
+            raise N.NativeError("the text plan runs all blocks")
+        N.check(self.lib.pv_text_forward(self._plan, inp.data_ptr(), B, int(run_head), taps, n_taps, ws.data_ptr(), ws.numel(),
+                                         out_ptr, stream),
+                "pv_text_forward")
+
+    def _pos_embed_view(self, model, B: int) -> torch.Tensor:
+        """hook_pos_embed: the parameter slice [T, d], no batch dimension (base_text_transformer.py:139)"""
+        return model.pos_embed.detach()[: self.cfg.context_length]

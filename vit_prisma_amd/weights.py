@@ -16,7 +16,7 @@ from typing import Dict, Mapping, Optional
 
 import torch
 
-from .configs import HookedViTConfig
+from .configs import HookedTextTransformerConfig, HookedViTConfig
 
 
 def _heads_in(w: torch.Tensor, cfg) -> torch.Tensor:
@@ -43,6 +43,18 @@ def _block(sd: Mapping[str, torch.Tensor], cfg, new: str, q, k, v, bq, bk, bv, o
     return out
 
 
+def _open_clip_blocks(sd: Mapping[str, torch.Tensor], cfg, old_layer_key: str) -> Dict[str, torch.Tensor]:
+    """open_clip's residual blocks under ``old_layer_key`` (either tower: weight_conversion.py:345-429)."""
+    new: Dict[str, torch.Tensor] = {}
+    for layer in range(cfg.n_layers):
+        old = f"{old_layer_key}.{layer}"
+        q, k, v = sd[old + ".attn.in_proj_weight"].chunk(3)
+        bq, bk, bv = sd[old + ".attn.in_proj_bias"].chunk(3)
+        new.update(_block(sd, cfg, f"blocks.{layer}", q, k, v, bq, bk, bv, old + ".attn.out_proj", None, old + ".ln_1",
+                          old + ".ln_2", old + ".mlp.c_fc", old + ".mlp.c_proj"))
+    return new
+
+
 def convert_open_clip_weights(old_state_dict: Mapping[str, torch.Tensor], cfg: HookedViTConfig) -> Dict[str, torch.Tensor]:
     sd = old_state_dict
     new: Dict[str, torch.Tensor] = {
@@ -54,12 +66,18 @@ def convert_open_clip_weights(old_state_dict: Mapping[str, torch.Tensor], cfg: H
         "ln_pre.w": sd["visual.ln_pre.weight"], "ln_pre.b": sd["visual.ln_pre.bias"],
         "head.W_H": sd["visual.proj"], "head.b_H": torch.zeros(cfg.n_classes),
     }
-    for layer in range(cfg.n_layers):
-        old = f"visual.transformer.resblocks.{layer}"
-        q, k, v = sd[old + ".attn.in_proj_weight"].chunk(3)
-        bq, bk, bv = sd[old + ".attn.in_proj_bias"].chunk(3)
-        new.update(_block(sd, cfg, f"blocks.{layer}", q, k, v, bq, bk, bv, old + ".attn.out_proj", None, old + ".ln_1",
-                          old + ".ln_2", old + ".mlp.c_fc", old + ".mlp.c_proj"))
+    new.update(_open_clip_blocks(sd, cfg, "visual.transformer.resblocks"))
+    return new
+
+
+def convert_open_clip_text_weights(old_state_dict: Mapping[str, torch.Tensor], cfg: HookedTextTransformerConfig) -> Dict[str, torch.Tensor]:
+    """open_clip's text tower (top-level keys of the CLIP state dict) -> HookedTextTransformer's state dict; same keys and values as
+    models/weight_conversion.py:316-342.  No ln_pre.* is written: load with strict=False."""
+    sd = old_state_dict
+    new = {"token_embed.weight": sd["token_embedding.weight"], "pos_embed": sd["positional_embedding"],
+           "ln_final.w": sd["ln_final.weight"], "ln_final.b": sd["ln_final.bias"],
+           "head.W_H": sd["text_projection"], "head.b_H": torch.zeros((cfg.n_classes,))}
+    new.update(_open_clip_blocks(sd, cfg, "transformer.resblocks"))
     return new
 
 
