@@ -673,7 +673,8 @@ int pv_sae_sync_shadows(pv_sae_plan* plan, pv_sae_state* st, int32_t from_transp
  * they take the exact fp32 GEMM + streaming top-k. */
 int pv_sae_encoder_is_filtered(const pv_sae_plan* plan);
 /* Debug / tests: byte offset of a named workspace region ("fb_count": uint32, tokens of the last encode that took the
- * exact fallback; "fb_list", "cand_cnt", "thr"), (size_t)-1 if unknown. */
+ * exact fallback; "fb_list", "cand_cnt", "thr"; of the dense steps "hidden" (f, later dH), "sae_in", "dY" and "dense_amax":
+ * 16 x 256 uint32 bit patterns of the split-fp16 form's partial operand maxima), (size_t)-1 if unknown. */
 size_t pv_debug_sae_ws_offset(const pv_sae_plan* plan, const char* name);
 
 /* Inference-side pieces for the module API (StandardSparseAutoencoder.encode/decode). */

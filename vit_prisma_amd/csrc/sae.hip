@@ -1123,6 +1123,9 @@ extern "C" size_t pv_debug_sae_ws_offset(const pv_sae_plan* plan, const char* na
     if (!strcmp(name, "cand_cnt")) return w.cand_cnt;
     if (!strcmp(name, "thr")) return w.thr;
     if (!strcmp(name, "hidden")) return w.hidden;
+    if (!strcmp(name, "dY")) return w.dY;
+    if (!strcmp(name, "sae_in")) return w.sae_in;
+    if (!strcmp(name, "dense_amax")) return w.dense_amax;          // PV_SAE_AMAX_TENSORS x 256 uint32 (bit patterns of partial maxima)
     return (size_t)-1;
 }
 
