@@ -529,7 +529,7 @@ int pv_sae_tp_bucket_unpack(pv_sae_plan* plan, const float* bucket, float* scala
  * every published CLIP SAE of the reference is, docs/sae_table.md) ---------------------------------------------------------
  * Same contract as pv_sae_step (forward + backward + statistics of one train step on N tokens, gradients WRITTEN into
  * st->g*, complete buffers), for feature activations that are not k-sparse: five dense GEMMs on the exact fp32 matrix
- * instruction with the elementwise work in their epilogues (sae_dense.hip).  plan->d.k is ignored.  flags:
+ * instruction with the elementwise work in their epilogues (sae_dense.hip; the GEMM: sae_dense_gemm.hip; ghost gradients: sae_ghost.hip).  plan->d.k is ignored.  flags:
  * PV_SAE_UPDATE_STATS, PV_SAE_RENORM_DECODER (set_decoder_norm_to_unit_norm is applied to W_dec in place, first).
  * scalars: 0 loss = mse + l1 (+ ghost), 1 mse_loss, 2 l0 (mean_n #(f > 0)), 4 l1_loss = l1_coefficient * mean_n ||f_n||_1,
  * 5 ghost residual loss (0 without pv_sae_ghost).
@@ -610,7 +610,7 @@ int pv_sae_relu_step(pv_sae_plan* plan, pv_sae_state* st, const float* x, int32_
                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* One train step of a gated SAE (batch_mean / n_global as in pv_sae_step: tokens may be sharded over ranks, the caller all-reduces
- * the flat gradient buffer): forward + backward + statistics on the dense GEMM kernel -- the shared
+ * the flat gradient buffer): forward + backward + statistics on the dense GEMM kernel (sae_gated.hip, both forms) -- the shared
  * product sae_in @ W_enc once (both paths in its epilogue), the two decoder products (feature_acts and relu(gate)) as ONE GEMM
  * over stacked rows, likewise their two backward products and the two terms of gW_dec.  Gradients WRITTEN into st->g* and
  * st->gt.g* (gb_enc = 0); flags: PV_SAE_UPDATE_STATS, PV_SAE_RENORM_DECODER (REQUIRED: the L1 term's decoder norms are taken

@@ -1,4 +1,5 @@
-"""Planted operand ranges for the dense SAE steps of csrc/sae_dense.hip (the ReLU + L1 step, its tanh-relu / lp_norm > 1 tail, the gated
+"""Planted operand ranges for the dense SAE steps of csrc/sae_dense.hip and csrc/sae_gated.hip on the GEMM of csrc/sae_dense_gemm.hip
+(the ReLU + L1 step, its tanh-relu / lp_norm > 1 tail, the gated
 step), a float64 reference with the absolute sums a bound needs, per-element bounds for both forms of ``dense_gemm_kernel`` (the exact
 fp32 matrix instruction and the split-fp16 one), a checker, and a numpy twin of the split GEMM with the slips it can be told to make.
 numpy on the CPU, importable without a GPU.

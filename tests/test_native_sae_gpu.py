@@ -957,7 +957,7 @@ def test_feature_parallel_simulated_world_equals_single_process_oracle(world, d_
 
 
 # ---------------------------------------------------------------------------------------------------
-# the dense fused step: ReLU + L1 SAEs (pv_sae_dense_step, csrc/sae_dense.hip)
+# the dense fused step: ReLU + L1 SAEs (pv_sae_dense_step, csrc/sae_dense.hip; ghost gradients: csrc/sae_ghost.hip)
 # ---------------------------------------------------------------------------------------------------
 # (the last four: the shape bench.py times this step at -- 768 -> 24576, 4096 tokens -- and the x64 SAEs every published CLIP-B/32 SAE of
 # the reference is, docs/sae_table.md:12-36 -- 768 -> 49152)

@@ -1,6 +1,6 @@
-"""The dense SAE steps of csrc/sae_dense.hip on planted operand ranges (tests/_sae_dense_cases.py): ``dense_step`` and ``gated_step`` through
-NativeSAE, in the split-fp16 form and in the exact fp32 form (forced through the tuning key dense_fp32, or taken by the kernels on their
-own at N % 4 != 0).  Every element of the reconstruction, of dH (left in the workspace), of every gradient tensor and the scalars are held
+"""The dense SAE steps of csrc/sae_dense.hip and csrc/sae_gated.hip (the GEMM: csrc/sae_dense_gemm.hip) on planted operand ranges
+(tests/_sae_dense_cases.py): ``dense_step`` and ``gated_step`` through NativeSAE, in the split-fp16 form and in the exact fp32 form
+(forced through the tuning key dense_fp32, or taken by the kernels on their own at N % 4 != 0).  Every element of the reconstruction, of dH (left in the workspace), of every gradient tensor and the scalars are held
 to a bound derived from the float64 reference's own absolute sums and the stated rounding model (no tensor-wide norm, nothing fitted);
 gates, firing counts and l0 exactly; ``exact_grid`` and ``no_firing`` add their exact assertions, ``shrinking`` the bit-identity with a fresh
 engine.  The split form's tracked operand maxima are read back and must be the tensors' own.  Every test prints its worst error / bound

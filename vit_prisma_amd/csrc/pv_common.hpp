@@ -229,7 +229,7 @@ struct PvTuning {
     int sae_exact = 0;       // 1: SAE encoder on the exact-fp32 MFMA GEMM + streaming top-k (the small-shape / fallback path)
     int sae_fold = 1;        // 0: pv_sae_step launches its small kernels one by one (the A/B of the fused pre-pass, SaePre, the scan as a role of
                              // the decode launch, ScanRole, the merged list sorts and the Adam pair's tail roles)
-    int dense_group = -1;    // tile order of the dense SAE GEMMs (sae_dense.hip): -1 auto (wide outputs: 4 row tiles per group), 0 = N fastest
+    int dense_group = -1;    // tile order of the dense SAE GEMMs (sae_dense_gemm.hip): -1 auto (wide outputs: 4 row tiles per group), 0 = N fastest
                              // everywhere (the order up to round 6's PMC pass), n = n row tiles per group
     int sae_inline_fb = 0;   // 1: the folded SAE step recomputes a token the filter cannot decide inside the select kernel (no fallback launches:
                              // - 14 us per step) -- off: ONE such token costs the step 0.3 ms of latency (its workgroup walks all features
@@ -246,7 +246,7 @@ struct PvTuning {
                              // stream): -1 auto = where the launch has more tiles than CUs, 0 = never, 1 = wherever it is legal
     int gemm_stagger = 0;    // A/B knob of the persistent form: start delay step between workgroups (units of 127 x 64 clocks), 0 = none
     int dense_fp32 = 0;      // 1: the dense SAE steps (ReLU + L1, gated) on the exact fp32 matrix instruction (round 5's form) instead of the
-                             // split-fp16 one (three fp16 products per fp32 product, fp32 accumulation): the A/B of sae_dense.hip
+                             // split-fp16 one (three fp16 products per fp32 product, fp32 accumulation): the A/B of sae_dense_gemm.hip
     int gemm_cus = 0;        // CUs a GEMM launch may count on (grid of the persistent form, rounds of the tile model): 0 = the device's; set by
                              // probes that run forwards on CU-masked streams (tools/cu_mask_forward_probe.py); a plan with a pipeline passes its own
 };

@@ -254,11 +254,6 @@ __global__ __launch_bounds__(256) void sae_prep_roles_kernel(const float* __rest
 // exact top-k per row by radix select on the order-preserving uint image of the floats
 // (TopK.forward, sae.py:795-810: torch.topk -> relu -> scatter; only the selected SET matters)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t f2ord(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 constexpr int TOPK_CAP = PV_TOPK_CAP;   // candidate list capacity of the fast path
 
 // Per-row exact top-k, streaming (no per-thread value cache -> ~40 VGPRs, full occupancy):
@@ -306,9 +301,8 @@ __device__ void sae_topk_row(const float* __restrict__ hidden, int32_t* __restri
 // decode + LN-out + loss partial + dY + dh    (one wave per token)
 // ------------------------------------------------------------------------------------------------
 // A wave owns a token; lane l owns the 16-byte column groups 4 l + 256 i (i < V4: d_in <= 256 V4), so every gathered
-// W_dec row is fetched as V4 16-byte loads per lane (1 KiB per wave-instruction), four rows in flight (ld4: sae_bwd.hpp).
+// W_dec row is fetched as V4 16-byte loads per lane (1 KiB per wave-instruction), four rows in flight (ld4, dot4: sae_bwd.hpp).
 // The CSR scan that rides in this launch as one more workgroup: ScanRole / scan_body_256 (sae_bwd.hpp).
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 // The optimizer state (both Adam moments, 302 MB) and the gradients are touched ONCE per step: streamed past the caches
 // (nontemporal), so that what the next step gathers by row -- W_dec, W_enc^T and its fp16 copy, 188 MB, written by the same
 // kernels -- is what stays in the 256 MB MALL.  -DPV_NO_NT (A/B builds): plain accesses.
@@ -1465,276 +1459,6 @@ int sae_sparse_tail(pv_sae_plan* plan, pv_sae_state* st, const float* x, int N, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// The gated step in sparse form (pv_sae_gated_step_sparse; the dense form and the mathematics: pv_sae_gated_step, sae_dense.hip).
-// A gated SAE's forward is sparse in the OPEN GATES: feature_acts, relu(gate_pre) and every gradient behind them vanish where
-// gate_pre <= 0 (sae.py:703-716, :773-792).  The selection (relu_select_kernel<GATED>) leaves, per token, the list of its open gates
-// with both values per pair {f = feature_acts, g = relu(gate_pre)}; from there the step is the k-sparse machinery with TWO decoder
-// terms per pair:
-//     decode (ONE gather of W_dec[j] per pair):  reconstruction = sum f W_dec[j] (+ LN-out, mse, dY, dM = (dY . W_dec[j]) [f > 0]),
-//                                                via the gate   = sum g W_dec[j] (aux loss against sae_in, dVia, dG = dVia . W_dec[j] + l1 / N)
-//     backward (bwd_walk<DUAL>):  gW_dec[j] = sum f dY[n] + g dVia[n],  gW_enc^T[j] = sum dP sae_in[n],  gb_enc[j] = sum dP = colsum(dP)
-//     with dP = dM e^r + dG (parked in gb_enc for gb_dec, as the dense form does)
-// ------------------------------------------------------------------------------------------------
-namespace {
-template <int V4>
-__global__ __launch_bounds__(256) void gated_decode_kernel(
-    const float* __restrict__ x, const float* __restrict__ sae_in, const float* __restrict__ W_dec, const float* __restrict__ b_dec,
-    const int32_t* __restrict__ idx, const float* __restrict__ valf, const float* __restrict__ valg, const float* __restrict__ mu,
-    const float* __restrict__ sd, const float* __restrict__ norm, float* __restrict__ sae_out, float* __restrict__ dY,
-    float* __restrict__ dVia, float* __restrict__ dM, float* __restrict__ dG, float* __restrict__ mse_part, float* __restrict__ aux_part,
-    int n_tok, int d, int k, float grad_scale /* 2 / (N d_in) */, float aux_scale /* 2 / N */, float dh_add /* l1 / N */,
-    const uint32_t* __restrict__ tok_cnt, const uint32_t* __restrict__ gate) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= n_tok) return;
-    if (*gate != 0u) return;
-    bool ok[V4];
-    int col[V4];
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-        col[i] = 4 * lane + 256 * i;
-        ok[i] = col[i] < d;
-    }
-    float4 af[V4], ag[V4];
-#pragma unroll
-    for (int i = 0; i < V4; ++i) { af[i] = make_float4(0.f, 0.f, 0.f, 0.f); ag[i] = af[i]; }
-    const int32_t* ir = idx + (int64_t)n * k;
-    const float* fr = valf + (int64_t)n * k;
-    const float* gr = valg + (int64_t)n * k;
-    const int k_walk = min(k, (int)((tok_cnt[n] + 3u) & ~3u));       // (slots beyond it are holes: g = 0)
-    for (int s = 0; s < k_walk; s += 4) {
-        float a[4], b[4];
-        float4 w[4][V4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int ju = ir[s + u];
-            a[u] = fr[s + u];
-            b[u] = gr[s + u];
-            const float* wr = W_dec + (int64_t)ju * d;
-#pragma unroll
-            for (int i = 0; i < V4; ++i) w[u][i] = ld4(wr + col[i], ok[i] && b[u] != 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)                       // (slot order: fixed)
-#pragma unroll
-            for (int i = 0; i < V4; ++i) {
-                af[i].x += a[u] * w[u][i].x; af[i].y += a[u] * w[u][i].y; af[i].z += a[u] * w[u][i].z; af[i].w += a[u] * w[u][i].w;
-                ag[i].x += b[u] * w[u][i].x; ag[i].y += b[u] * w[u][i].y; ag[i].z += b[u] * w[u][i].z; ag[i].w += b[u] * w[u][i].w;
-            }
-    }
-    const float m = mu[n], sdv = sd[n], nf = norm[n];
-    float lf = 0.f, lg = 0.f;
-    float4 gf[V4], gg[V4];
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-        gf[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        gg[i] = gf[i];
-        if (ok[i]) {
-            const float4 bd = *reinterpret_cast<const float4*>(b_dec + col[i]);
-            const float4 xv = *reinterpret_cast<const float4*>(x + (int64_t)n * d + col[i]);
-            const float4 sv = *reinterpret_cast<const float4*>(sae_in + (int64_t)n * d + col[i]);
-            float4 o, e;
-            o.x = (af[i].x + bd.x) * sdv + m; o.y = (af[i].y + bd.y) * sdv + m;          // as sae_decode_kernel / gated_finish_kernel
-            o.z = (af[i].z + bd.z) * sdv + m; o.w = (af[i].w + bd.w) * sdv + m;
-            e.x = o.x - xv.x; e.y = o.y - xv.y; e.z = o.z - xv.z; e.w = o.w - xv.w;
-            if (sae_out) *reinterpret_cast<float4*>(sae_out + (int64_t)n * d + col[i]) = o;
-            lf += (e.x * e.x) / nf + (e.y * e.y) / nf + (e.z * e.z) / nf + (e.w * e.w) / nf;
-            gf[i].x = grad_scale * e.x / nf * sdv; gf[i].y = grad_scale * e.y / nf * sdv;
-            gf[i].z = grad_scale * e.z / nf * sdv; gf[i].w = grad_scale * e.w / nf * sdv;
-            *reinterpret_cast<float4*>(dY + (int64_t)n * d + col[i]) = gf[i];
-            e.x = ag[i].x + bd.x - sv.x; e.y = ag[i].y + bd.y - sv.y; e.z = ag[i].z + bd.z - sv.z; e.w = ag[i].w + bd.w - sv.w;
-            lg += e.x * e.x + e.y * e.y + e.z * e.z + e.w * e.w;                          // sae.py:786-792
-            gg[i].x = aux_scale * e.x; gg[i].y = aux_scale * e.y; gg[i].z = aux_scale * e.z; gg[i].w = aux_scale * e.w;
-            *reinterpret_cast<float4*>(dVia + (int64_t)n * d + col[i]) = gg[i];
-        }
-    }
-    lf = wave_sum(lf);
-    lg = wave_sum(lg);
-    if (lane == 0) { mse_part[n] = lf; aux_part[n] = lg; }
-    for (int s = 0; s < k_walk; s += 4) {
-        float df[4], dg[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int ju = ir[s + u];
-            const bool live = gr[s + u] > 0.f;                    // (wave-uniform)
-            const float* wr = W_dec + (int64_t)ju * d;
-            float tf = 0.f, tg = 0.f;
-#pragma unroll
-            for (int i = 0; i < V4; ++i) {
-                const float4 wv = ld4(wr + col[i], ok[i] && live);
-                tf += dot4(gf[i], wv);
-                tg += dot4(gg[i], wv);
-            }
-            df[u] = tf;
-            dg[u] = tg;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                df[u] += __shfl_xor(df[u], o, 64);
-                dg[u] += __shfl_xor(dg[u], o, 64);
-            }
-        if (lane < 4) {
-            const float sf = lane == 0 ? df[0] : (lane == 1 ? df[1] : (lane == 2 ? df[2] : df[3]));
-            const float sg = lane == 0 ? dg[0] : (lane == 1 ? dg[1] : (lane == 2 ? dg[2] : dg[3]));
-            dM[(int64_t)n * k + s + lane] = fr[s + lane] > 0.f ? sf : 0.f;                    // (dY W_dec^T) [f > 0]
-            dG[(int64_t)n * k + s + lane] = gr[s + lane] > 0.f ? sg + dh_add : 0.f;           // (dVia W_dec^T + l1 / N) [gate_pre > 0]
-        }
-    }
-}
-
-// dP = dM e^r + dG per pair (sae.py:708-712 backwards); holes (never written by the decode kernel) -> 0
-__global__ __launch_bounds__(256) void gated_pairs_kernel(const int32_t* __restrict__ idx, const uint32_t* __restrict__ wpos,
-                                                          const float* __restrict__ dM, const float* __restrict__ dG,
-                                                          const float* __restrict__ r_mag, float* __restrict__ dP, int n_pairs,
-                                                          const uint32_t* __restrict__ gate) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_pairs || *gate != 0u) return;
-    dP[i] = wpos[i] != 0xffffffffu ? dM[i] * expf(r_mag[idx[i]]) + dG[i] : 0.f;
-}
-
-// per feature, over its list (ascending token order): gb_gate = sum dG, gb_mag = sum dM, gr_mag = sum dM (mag_pre - b_mag) = sum dM f -
-// b_mag gb_mag, pgsum = sum relu(gate_pre) (the decoder-norm factor of the L1 term), the firing count of feature_acts + the
-// statistics (train_sae.py:356-361).  One wave per feature.
-__global__ __launch_bounds__(256) void gated_feat_kernel(const uint32_t* __restrict__ offs, const int32_t* __restrict__ pairs,
-                                                         const float* __restrict__ valf, const float* __restrict__ valg,
-                                                         const float* __restrict__ dM, const float* __restrict__ dG,
-                                                         const float* __restrict__ b_mag, int F, float* __restrict__ gb_gate,
-                                                         float* __restrict__ gb_mag, float* __restrict__ gr_mag, float* __restrict__ pgsum,
-                                                         float* __restrict__ fire_count, float* __restrict__ act_freq,
-                                                         float* __restrict__ n_since_fired, int update_stats,
-                                                         const uint32_t* __restrict__ gate) {
-    if (*gate != 0u) return;
-    const int lane = threadIdx.x & 63;
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= F) return;
-    const uint32_t beg = offs[j], end = offs[j + 1];
-    float sg = 0.f, sm = 0.f, smf = 0.f, sp = 0.f, fired = 0.f;
-#pragma unroll 4
-    for (uint32_t q = beg + lane; q < end; q += 64) {      // (unrolled: the gathers of four trips in flight; the sums in order)
-        const int p = pairs[q];
-        const float f = valf[p], m = dM[p];
-        sg += dG[p];
-        sm += m;
-        smf += m * f;
-        sp += valg[p];
-        fired += f > 0.f ? 1.f : 0.f;
-    }
-    sg = wave_sum(sg); sm = wave_sum(sm); smf = wave_sum(smf); sp = wave_sum(sp); fired = wave_sum(fired);
-    if (lane != 0) return;
-    gb_gate[j] = sg;
-    gb_mag[j] = sm;
-    gr_mag[j] = smf - b_mag[j] * sm;
-    pgsum[j] = sp;
-    if (fire_count) fire_count[j] = fired;
-    if (update_stats) {
-        act_freq[j] += fired;
-        n_since_fired[j] = fired > 0.f ? 0.f : n_since_fired[j] + 1.f;
-    }
-}
-
-// scalars: 1 mse, 6 aux, 4 l1, 2 l0, 0 their sum (sae.py:748); fixed summation order
-__global__ __launch_bounds__(256) void gated_sparse_scalars_kernel(const float* __restrict__ mse_part, const float* __restrict__ aux_part,
-                                                                   const float* __restrict__ l1part, const float* __restrict__ l0part,
-                                                                   int n_tok, float s_mse, float s_aux, float s_l1, float s_l0,
-                                                                   float* __restrict__ scalars, const uint32_t* __restrict__ gate) {
-    if (*gate != 0u) return;
-    __shared__ float red[4][4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float a = 0.f, b = 0.f, c = 0.f, e = 0.f;
-#pragma unroll 4
-    for (int i = threadIdx.x; i < n_tok; i += 256) { a += mse_part[i]; b += aux_part[i]; c += l1part[i]; e += l0part[i]; }
-    a = wave_sum(a); b = wave_sum(b); c = wave_sum(c); e = wave_sum(e);
-    if (lane == 0) { red[0][wv] = a; red[1][wv] = b; red[2][wv] = c; red[3][wv] = e; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float mse = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * s_mse;
-        const float aux = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) * s_aux;
-        const float l1 = ((red[2][0] + red[2][1]) + (red[2][2] + red[2][3])) * s_l1;
-        scalars[1] = mse; scalars[6] = aux; scalars[4] = l1;
-        scalars[2] = ((red[3][0] + red[3][1]) + (red[3][2] + red[3][3])) * s_l0;
-        scalars[0] = mse + l1 + aux;
-    }
-}
-}  // namespace
-
-GatedSparseWs gated_sparse_carve(const pv_sae_desc& d, int n_tokens, int cap) {
-    GatedSparseWs w;
-    w.rw = relu_carve(d, n_tokens, cap);
-    size_t off = w.rw.total;
-    auto take = [&](size_t bytes) { size_t o = off; off += (size_t)pv_align_up((int64_t)bytes, 256); return o; };
-    const size_t N = (size_t)n_tokens, P = N * (size_t)cap;
-    w.valg = take(P * 4);
-    w.dM = take(P * 4);
-    w.dG = take(P * 4);
-    w.l0part = take(N * 4);
-    w.total = off + 256;
-    return w;
-}
-
-// dYs: [2N, d_in] = [dY; dVia] (the dense form's layout), auxpart: [N], pgsum: [d_sae] -- regions of the gated scratch the two
-// forms share, so that everything behind them (the decoder-norm term, gb_dec) runs once.  Leaves colsum(dP) in st->gb_enc.
-int sae_gated_sparse(pv_sae_plan* plan, pv_sae_state* st, const float* x, int N, int n_global, int cap, float l1_coefficient,
-                     int update_stats, unsigned char* rwb, const GatedSparseWs& gs, pv_sae_out* out, unsigned char* wsb, const SaeWs& ws,
-                     float* dYs, float* auxpart, float* pgsum, hipStream_t stream) {
-    const pv_sae_desc& d = plan->d;
-    const pv_sae_gated& t = st->gt;
-    const ReluWs& rw = gs.rw;
-    const int D = d.d_in, F = d.d_sae, n_pairs = N * cap;
-    const float ng = (float)n_global;
-    uint32_t* mode = (uint32_t*)(rwb + rw.mode);
-    int32_t* idx = (int32_t*)(rwb + rw.idx);
-    float* valf = (float*)(rwb + rw.val);
-    float* valg = (float*)(rwb + gs.valg);
-    uint32_t* wpos = (uint32_t*)(rwb + rw.wpos);
-    uint32_t* tok_cnt = (uint32_t*)(rwb + rw.tok_cnt);
-    float* l1part = (float*)(rwb + rw.l1part);
-    float* l0part = (float*)(rwb + gs.l0part);
-    float* dM = (float*)(rwb + gs.dM);
-    float* dG = (float*)(rwb + gs.dG);
-    float* dP = (float*)(rwb + rw.dh);
-    const float* sae_in = (const float*)(wsb + ws.sae_in);
-    float* dVia = dYs + (size_t)N * D;
-    int rc;
-    {
-        ProfScope prof(PV_PROF_SAE_ENC, stream, 2.0 * N * (double)D * F, ((double)N * D + (double)D * F) * 2.0);
-        rc = sae_encode_relu(d, st, N, cap, idx, valf, tok_cnt, l1part, (uint32_t*)(rwb + rw.cand_cnt), rwb + rw.cand,
-                             (uint32_t*)(wsb + ws.cnt), wpos, mode, (const float*)out->scalars, wsb, ws, stream, l0part, valg);
-        if (rc) return rc;
-    }
-    ProfScope prof(PV_PROF_SAE_BWD, stream, 6.0 * n_pairs * (double)D * 2.0, 0.0);
-    const dim3 grid((N + 3) / 4), block(256);
-#define CALL(V)                                                                                                                   \
-    hipLaunchKernelGGL((gated_decode_kernel<V>), grid, block, 0, stream, x, sae_in, (const float*)st->W_dec, (const float*)st->b_dec, \
-                       (const int32_t*)idx, (const float*)valf, (const float*)valg, (const float*)(wsb + ws.mu),                    \
-                       (const float*)(wsb + ws.sd), (const float*)(wsb + ws.norm), out->sae_out, dYs, dVia, dM, dG,                 \
-                       (float*)(wsb + ws.loss_part), auxpart, N, D, cap, 2.0f / (ng * (float)D), 2.0f / ng, l1_coefficient / ng,   \
-                       (const uint32_t*)tok_cnt, (const uint32_t*)mode)
-    V4_DISPATCH(D, CALL);
-#undef CALL
-    PV_LAUNCH_CHECK("gated_decode_kernel");
-    hipLaunchKernelGGL(gated_pairs_kernel, dim3((n_pairs + 255) / 256), block, 0, stream, (const int32_t*)idx, (const uint32_t*)wpos,
-                       (const float*)dM, (const float*)dG, (const float*)t.r_mag, dP, n_pairs, (const uint32_t*)mode);
-    PV_LAUNCH_CHECK("gated_pairs_kernel");
-    SaeBwd b;                                                       // (statistics and fire_count: gated_feat_kernel)
-    b.N = N; b.k = cap; b.idx = idx; b.val = valf; b.dY = dYs; b.sae_in = sae_in; b.scalars = out->scalars;
-    b.tail = relu_tail(rwb, rw);                                    // (tail.dh = dP)
-    b.gate = mode; b.val_b = valg; b.dY_b = dVia;
-    rc = sae_csr_backward(plan, st, b, wsb, ws, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(gated_feat_kernel, dim3((F + 3) / 4), block, 0, stream, (const uint32_t*)(wsb + ws.offs), (const int32_t*)b.tail.pairs,
-                       (const float*)valf, (const float*)valg, (const float*)dM, (const float*)dG, (const float*)t.b_mag, F, t.gb_gate,
-                       t.gb_mag, t.gr_mag, pgsum, out->fire_count, st->act_freq_scores, st->n_fwd_since_fired, update_stats,
-                       (const uint32_t*)mode);
-    hipLaunchKernelGGL(gated_sparse_scalars_kernel, dim3(1), block, 0, stream, (const float*)(wsb + ws.loss_part), (const float*)auxpart,
-                       (const float*)l1part, (const float*)l0part, N, 1.0f / (ng * (float)D), 1.0f / ng, l1_coefficient / ng,
-                       1.0f / (float)N, out->scalars, (const uint32_t*)mode);
-    PV_LAUNCH_CHECK("gated sparse kernels");
-    return PV_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
 // The TOP-K form of the gated SAE (activation_fn_str = "topk" on a GatedSparseAutoencoder, sae.py:699-716, 741-745, 773-778):
 //     feature_acts = [gate_pre > 0] TopK(mag_pre),   mag_pre  = sae_in (W_enc e^r_mag) + b_mag
 //     pi_gate_act  = TopK(gate_pre),                 gate_pre = sae_in W_enc + b_gate
@@ -1930,11 +1654,6 @@ __global__ __launch_bounds__(256) void gated_topk_scalars_kernel(const float* __
         scalars[0] = mse + aux;
     }
 }
-
-__global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ y, const float* __restrict__ x, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) y[i] += x[i];
-}
 }  // namespace
 
 extern "C" size_t pv_sae_gated_topk_scratch_bytes(const pv_sae_plan* plan, int32_t n_tokens) {
@@ -2037,13 +1756,8 @@ extern "C" int pv_sae_gated_topk_step(pv_sae_plan* plan, pv_sae_state* st, const
                            (const float*)l0part, N, 1.0f / (ng * (float)D), 1.0f / ng, 1.0f / (float)N, out->scalars);
         PV_LAUNCH_CHECK("top-k gated kernels");
         // gb_dec = colsum(dY) + 2 colsum(dVia) - W_enc colsum(dP) (as pv_sae_gated_step); b_enc takes no part
-        rc = sae_gbdec(d, st, dY2, N, wsb, ws, stream);
+        rc = sae_gated_gbdec(d, st, dY2, N, (float*)(gb + gw.tmpd), (float*)(gb + gw.cspart), wsb, ws, stream);
         if (rc) return rc;
-        rc = sae_colsum(dY2 + (size_t)N * D, N, D, (float*)(gb + gw.tmpd), 2.0f, (float*)(gb + gw.cspart), stream);
-        if (rc) return rc;
-        hipLaunchKernelGGL(axpy_kernel, dim3((D + 255) / 256), block, 0, stream, st->gb_dec, (const float*)(gb + gw.tmpd), D);
-        PV_LAUNCH_CHECK("axpy_kernel");
-        PV_HIP_CHECK(hipMemsetAsync(st->gb_enc, 0, (size_t)F * 4, stream));
     }
     return PV_OK;
 }

@@ -1,4 +1,5 @@
-// Shared definitions of the SAE step (sae.hip: prep / decode / Adam; sae_bwd.hip: the sparse backward; sae_enc.hip: the encoder + top-k).
+// Shared definitions of the SAE step (sae.hip: prep / decode / Adam; sae_bwd.hip: the sparse backward; sae_enc.hip: the encoder + top-k;
+// sae_dense.hip, sae_dense_gemm.hip, sae_ghost.hip, sae_gated.hip: the dense ReLU + L1 step, its GEMM, ghost gradients, the gated step).
 #pragma once
 #include "gemm.hpp"
 #include "prof.hpp"
@@ -35,8 +36,8 @@ struct SaePre {
 
 struct SaeWs {
     size_t total;
-    size_t dense_colpart, dense_rowpart, dense_kpart;     // sae_dense.hip: column partials [N/64][d_sae], per-wave sums, split-K partials
-    size_t dense_amax;                                    // sae_dense.hip: PV_SAE_AMAX_TENSORS x 256 partial maxima (operand scales of the split-fp16 GEMMs)
+    size_t dense_colpart, dense_rowpart, dense_kpart;     // sae_dense.hip, sae_gated.hip: column partials [N/64][d_sae], per-wave sums, split-K partials
+    size_t dense_amax;                                    // sae_dense_gemm.hpp: PV_SAE_AMAX_TENSORS x 256 partial maxima (operand scales of the split-fp16 GEMMs)
     size_t dense_lp_part, dense_lp_tok, dense_lp_loss;    // sae_dense.hip, lp_norm > 1: [N][d_sae / 64] sums of f^p, [N] gradient factors, [N] norms
     size_t hidden, sae_in, dY, mu, sd, norm, dh, loss_part, cnt, offs, cursor, wpos, long_list, n_long, seg_range, seg_rows, seg_b, pairs, colpart, colsum, batch_mean, sqpart, rowsq;
     // fast encoder (sae_enc.hip)
@@ -265,15 +266,10 @@ int sae_encode_relu(const pv_sae_desc& d, const pv_sae_state* st, int N, int cap
                     float* l1part, uint32_t* cand_cnt, void* cand, uint32_t* feat_cnt, uint32_t* wpos, uint32_t* mode,
                     const float* prev_scalars, unsigned char* wsb, const SaeWs& ws, hipStream_t stream, float* l0part = nullptr,
                     float* valg = nullptr);
-// sae.hip: the gated step in sparse form (pv_sae_gated_step_sparse; see the definition)
-struct GatedSparseWs {
-    ReluWs rw;
-    size_t total, valg, dM, dG, l0part;
-};
-GatedSparseWs gated_sparse_carve(const pv_sae_desc& d, int n_tokens, int cap);
-int sae_gated_sparse(pv_sae_plan* plan, pv_sae_state* st, const float* x, int N, int n_global, int cap, float l1_coefficient,
-                     int update_stats, unsigned char* rwb, const GatedSparseWs& gs, pv_sae_out* out, unsigned char* wsb, const SaeWs& ws,
-                     float* dYs, float* auxpart, float* pgsum, hipStream_t stream);
+// sae_gated.hip: behind every gated step (dYs = [dY; dVia], colsum(dP) in gb_enc): gb_dec = colsum(dY) + 2 colsum(dVia) - W_enc colsum(dP), gb_enc = 0
+int sae_gated_gbdec(const pv_sae_desc& d, const pv_sae_state* st, const float* dYs, int N, float* tmpd, float* cspart, unsigned char* wsb,
+                    const SaeWs& ws, hipStream_t stream);
+void sae_set_u32(uint32_t* p, uint32_t v, hipStream_t stream);      // sae_dense.hip: *p = v (the mode word of a step that has no sparse form)
 // sae.hip: everything of the k-sparse step behind the selection (see the definition)
 int sae_sparse_tail(pv_sae_plan* plan, pv_sae_state* st, const float* x, int N, int n_global, int k, const int32_t* topk_idx,
                     const float* topk_val, float* sae_out, float* scalars, float* fire_count, int update_stats, bool sparse,
@@ -283,7 +279,7 @@ int sae_sparse_tail(pv_sae_plan* plan, pv_sae_state* st, const float* x, int N, 
 // sae.hip: dec_inv_norm[j] = 1 / ||W_dec[j]|| (the read-only half of set_decoder_norm_to_unit_norm)
 int sae_dec_inv_norm(const pv_sae_desc& d, const pv_sae_state* st, hipStream_t stream);
 
-// sae.hip, shared with sae_dense.hip: see the definitions
+// sae.hip, shared with sae_dense.hip, sae_ghost.hip and sae_gated.hip: see the definitions
 // pre (with st): the fused pre-pass of the filtered top-k step, see SaePre -- ws.norm and the finished batch mean are left to later launches
 int sae_prep(const pv_sae_desc& d, const float* x, const float* b_dec, const float* batch_mean, int N, bool want_filter_inputs,
              unsigned char* wsb, const SaeWs& ws, hipStream_t stream, int d_true = 0, SaePre* pre = nullptr,

@@ -1,6 +1,6 @@
 // The sparse backward of the k-sparse SAE steps (sae_bwd.hip): the CSR by feature of the kept (token, slot) pairs and the gradient
 // kernels behind it.  Here: what its callers fill in (SaeBwd), the sizes the workspace carvers need, and the device bodies that kernels
-// of sae.hip and of sae_bwd.hip both run.
+// of sae.hip, sae_bwd.hip and sae_gated.hip share.
 #pragma once
 #include "sae.hpp"
 
@@ -73,6 +73,7 @@ namespace {
 __device__ __forceinline__ float4 ld4(const float* p, bool ok) {
     return ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
+__device__ __forceinline__ float dot4(const float4& a, const float4& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 
 // column sums of a [rows][d] fp32 matrix (deterministic two-stage reduction).
 // stage 1: partial[blk][c] over CS_ROWS-row blocks -- rows / 16 workgroups (256 at N = 4096: every CU busy), 16

@@ -809,7 +809,7 @@ __global__ __launch_bounds__(256) void sae_fb_hidden_kernel(const float* __restr
 // error band of the fp16 product, see the file header: exact_j > 0  =>  a_j > -B_n), every survivor is re-scored EXACTLY in fp32
 // against W_encT, and the ones whose exact value is positive are the token's activations -- values those of the exact fp32
 // encoder.  A token's list holds at most `cap` pairs; a token with more positives than that, a candidate slot that overflowed or
-// more than PV_SAE_CAND_CAP survivors raise the step's `mode` word: the step then runs on the dense GEMMs instead (sae_dense.hip),
+// more than PV_SAE_CAND_CAP survivors raise the step's `mode` word: the step then runs on the dense GEMMs instead (sae_dense.hip, sae_gated.hip),
 // so nothing is ever approximated.
 // ---------------------------------------------------------------------------------------------------
 // mode[0] = the step's mode word, mode[1] = dense steps in a row whose sparse attempt was skipped.  The attempt itself costs ~0.5 ms when

@@ -137,10 +137,10 @@ def sae_bench_leg(dev: torch.device, dist=None, steps: int = 20, warmup: int = 5
     if relu:
         dense_steps = int(n_dense.item())
         sparse_steps = steps - dense_steps
-        # dense steps: five fp32 MFMA GEMMs of 2 N d_in d_sae FLOP each (sae_dense.hip), bound by the fp32 matrix peak; sparse steps:
+        # dense steps: five fp32 MFMA GEMMs of 2 N d_in d_sae FLOP each (sae_dense.hip, sae_dense_gemm.hip), bound by the fp32 matrix peak; sparse steps:
         # the top-k step's traffic (1.4 GB of algorithmic HBM bytes), bound by HBM
         if dense_steps == steps:
-            # since round 6 the five GEMMs run on the fp16 matrix pipe as three fp16 products per fp32 product (split-fp16, sae_dense.hip):
+            # since round 6 the five GEMMs run on the fp16 matrix pipe as three fp16 products per fp32 product (split-fp16, sae_dense_gemm.hip):
             # the roof is the dense fp16 MFMA peak over the 30 N d_in d_sae fp16 FLOP issued; the algorithmic (fp32-equivalent) rate
             # and its fraction of the fp32 matrix peak -- the roof of round 5's form -- stand beside it
             flops = 10.0 * n_local * D_IN * D_SAE

@@ -197,7 +197,7 @@ class VisionSAETrainer:
     # ---- native engine ----------------------------------------------------------------------------
     def _native_kind(self, sae, x: torch.Tensor) -> Optional[str]:
         """Which fused HIP step serves this SAE: "topk" (k-sparse step, sae.hip), "relu" (dense ReLU + L1 step,
-        sae_dense.hip), "gated" (the gated SAE's step: sparse where the batch allows it, sae.hip / sae_dense.hip) or None (PyTorch path: the top-k
+        sae_dense.hip), "gated" (the gated SAE's step: sparse where the batch allows it, sae_gated.hip) or None (PyTorch path: the top-k
         gated form / other activations / d_out != d_in / CPU)."""
         cfg = sae.cfg
         from .variants import Transcoder
