@@ -26,6 +26,16 @@
 //   => B_n = ||x_n||_2 (C1 Wmax + C2) + C2 Wmax,  C1 = max(1.25e-3, 2^-10 (1 + 2^-12) + 5 K 2^-24) (enc_c1(K): 1.25e-3 up to K = 916,
 //      1.36e-3 at K = 1280),
 //      C2 = 2^-25 sqrt(K),  Wmax = max_j ||W_enc[:, j]||_2 (maintained by the Adam kernel as enc_colsq).
+//   The two compared values are each acc + b_enc[j] rounded once to fp32: 2 x 2^-24 |a_j|, covered by a rounding term 4.8e-7 |v| on top of
+//   B_n, v being the size of the sums compared.  sae_thr_kernel knows s_q (the q-th largest SAMPLED value) and leaves 2 B_n(|s_q|) in band[];
+//   sae_select_kernel compares around t, the k-th largest filter value, and adds 9.6e-7 (|t| - |s_q|) where that is positive.  (Until the
+//   planted suite, tests/_sae_encoder_cases.py ``bias_dominated``, the band around t carried the term at |s_q| only: nine features with
+//   b_enc = 2^20 off the sample, sampled values near 1 -- the exact largest came back one fp32 step of 2^20 below t in the filter,
+//   300 bands away, was never re-scored, and the row returned a wrong index set with no fallback.)  The threshold needs no such change:
+//   v - 2 c |v| increases with v, so t >= s_q gives t - 2 B_n(|t|) >= s_q - 2 B_n(|s_q|) = T_n and the band below t is in the list.
+//   The same suite holds the band to its factor: rows whose loser beats the winner by 1.05 B_n in the filter (operand rounding on disjoint
+//   halves of x reaches 1.1 B_n at most) lose a winner under a band of B_n or a C1 below 2^-10, at d_in 64 and at 1032 where enc_c1
+//   leaves its floor.  The ReLU threshold -B_n needs no rounding term: fl32 is monotone, so exact_j > 0 implies a_j >= fl32(-B_n).
 // Rows with |x| beyond the fp16 range get B = inf (-> fallback); a weight beyond it makes its column norm inf (-> every
 // row falls back): slow, never wrong.
 #include <atomic>
@@ -643,7 +653,9 @@ __global__ __launch_bounds__(256, PV_SEL_WAVES) void sae_select_kernel(
     __syncthreads();
     const float t = ord2f(sh_t);
     bad = bad || !(t >= sq[row]);                              // band below t not guaranteed to be in the list (or NaN)
-    const float lo = t - band[row];
+    // the band's rounding term (file header) as sae_thr_kernel left it covers sums the size of s_q; the sums compared here are the size
+    // of t, which is far larger where the row's large values come from b_enc and sit off the sample
+    const float lo = t - (band[row] + 9.6e-7f * fmaxf(fabsf(t) - fabsf(sq[row]), 0.f));
     if (!bad) {
         for (uint32_t c = tid; c < nc; c += 256) {
             if (ord2f(ckey[c]) >= lo) {
