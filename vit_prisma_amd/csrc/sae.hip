@@ -2122,6 +2122,17 @@ extern "C" int pv_sae_apply(pv_sae_plan* plan, pv_sae_state* st, const float* sc
     hipStream_t stream = (hipStream_t)stream_;
     const pv_sae_desc& d = plan->d;
     PV_REQUIRE(j_lo >= 0 && j_lo <= j_hi && j_hi <= d.d_sae, "feature range");
+    // (every check stands in front of the first launch: a call that returns an error has not touched the state)
+    if (sae_is_tc(st)) {
+        const pv_sae_transcoder& t = st->tc;
+        PV_REQUIRE(t.gb_dec_out && t.mb_dec_out && t.vb_dec_out && (!t.W_skip || (t.gW_skip && t.mW_skip && t.vW_skip)), "transcoder Adam state");
+    }
+    if (sae_is_gated(st)) {
+        const pv_sae_gated& t = st->gt;
+        PV_REQUIRE(t.r_mag && t.b_mag && t.gb_gate && t.gr_mag && t.gb_mag && t.mb_gate && t.mr_mag && t.mb_mag && t.vb_gate && t.vr_mag && t.vb_mag,
+                   "gated Adam state");
+        PV_REQUIRE(j_lo == 0 && j_hi == d.d_sae, "gated SAE: the whole feature range");
+    }
     AdamC c;
     c.lr = lr; c.b1 = 0.9f; c.b2 = 0.999f; c.eps = 1e-8f; c.max_norm = max_grad_norm;
     c.bc1 = (float)(1.0 - pow(0.9, (double)step));
@@ -2156,7 +2167,6 @@ extern "C" int pv_sae_apply(pv_sae_plan* plan, pv_sae_state* st, const float* sc
         hipLaunchKernelGGL(adam_vec2_kernel, dim3(v2.nb0 + (d.d_in + 255) / 256), block, 0, stream, v2, scalars, c);
     if (sae_is_tc(st)) {                                               // transcoder: plain Adam on the decoder's own bias and the skip matrix
         const pv_sae_transcoder& t = st->tc;
-        PV_REQUIRE(t.gb_dec_out && t.mb_dec_out && t.vb_dec_out && (!t.W_skip || (t.gW_skip && t.mW_skip && t.vW_skip)), "transcoder Adam state");
         hipLaunchKernelGGL(adam_vec_kernel, dim3((d.d_in + 255) / 256), block, 0, stream, t.b_dec_out, (const float*)t.gb_dec_out,
                            t.mb_dec_out, t.vb_dec_out, scalars, c, 0, d.d_in);
         if (t.W_skip)
@@ -2165,9 +2175,6 @@ extern "C" int pv_sae_apply(pv_sae_plan* plan, pv_sae_state* st, const float* sc
     }
     if (sae_is_gated(st)) {                                            // gated SAE: plain Adam on b_gate, r_mag, b_mag
         const pv_sae_gated& t = st->gt;
-        PV_REQUIRE(t.r_mag && t.b_mag && t.gb_gate && t.gr_mag && t.gb_mag && t.mb_gate && t.mr_mag && t.mb_mag && t.vb_gate && t.vr_mag && t.vb_mag,
-                   "gated Adam state");
-        PV_REQUIRE(j_lo == 0 && j_hi == d.d_sae, "gated SAE: the whole feature range");
         const dim3 gv((d.d_sae + 255) / 256);
         hipLaunchKernelGGL(adam_vec_kernel, gv, block, 0, stream, t.b_gate, (const float*)t.gb_gate, t.mb_gate, t.vb_gate, scalars, c, 0, d.d_sae);
         hipLaunchKernelGGL(adam_vec_kernel, gv, block, 0, stream, t.r_mag, (const float*)t.gr_mag, t.mr_mag, t.vr_mag, scalars, c, 0, d.d_sae);

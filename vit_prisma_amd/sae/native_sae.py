@@ -589,11 +589,11 @@ class NativeSAE:
 
     def apply(self, lr: float, max_grad_norm: Optional[float], j_lo: int = 0, j_hi: Optional[int] = None) -> None:
         """clip -> project -> Adam for the features [j_lo, j_hi) (default: all) and b_dec."""
-        self.adam_step += 1
         st = self._state()
         N.check(self.lib.pv_sae_apply(self._plan, C.byref(st), self.scalars.data_ptr(),
-                                      float(max_grad_norm) if max_grad_norm else -1.0, float(lr), self.adam_step,
+                                      float(max_grad_norm) if max_grad_norm else -1.0, float(lr), self.adam_step + 1,
                                       int(j_lo), int(self.d_sae if j_hi is None else j_hi), self._stream()), "pv_sae_apply")
+        self.adam_step += 1                                       # (only a call that succeeded is a step)
         self._grad_fresh = False
         self._sq_fused = False
         full = j_lo == 0 and (j_hi is None or j_hi == self.d_sae)
