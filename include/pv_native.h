@@ -49,8 +49,8 @@ extern "C" {
  * 24: pv_vit_desc.pooling, PV_ATTN_MAX_TOKENS = 2048 (was 640);
  * 25: the supported attention shapes gain the wide heads, 64 < d_head <= 128 with d_head % 8 == 0 (CLIP ViT-H / g / bigG-14)).
  * Purely ADDITIVE exports do not bump it: the text tower (pv_text_desc, pv_text_weights, pv_text_plan_create,
- * pv_text_plan_set_weights, pv_text_forward) and pv_attention arrived at 25 and left every existing struct layout, signature, slot
- * value and flag as it was, so a caller written against 25 runs unchanged; the Python binding checks the build id besides. */
+ * pv_text_plan_set_weights, pv_text_forward), pv_attention and the logit lens (pv_logit_lens, pv_logit_lens_workspace_bytes,
+ * PV_LENS_MAX_STACK) arrived at 25 and left every existing struct layout, signature, slot value and flag as it was, so a caller written against 25 runs unchanged; the Python binding checks the build id besides. */
 #define PV_ABI_VERSION 25
 int pv_abi_version(void);
 /* Hash of the sources this binary was built from (sha256 over the .hip / .hpp files of vit_prisma_amd/csrc and this header, names and
@@ -703,6 +703,37 @@ int pv_clip_preprocess(const uint8_t* images, int32_t B, int32_t H, int32_t W, c
                        int32_t ksize_x, const int32_t* ybounds, const int32_t* ytaps, int32_t ksize_y, int32_t new_w,
                        int32_t new_h, int32_t left, int32_t top, int32_t S, const float* mean3_host, const float* std3_host,
                        int32_t out_dtype, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Patch-level logit lens (prisma_tools/logit_lens.py)                                         */
+/* ------------------------------------------------------------------------------------------ */
+
+/* Most stack entries of one call: 2 * n_layers + 1 with incl_mid, 97 for bigG-14's 48 layers.  The tap pointers travel to the
+ * kernels by value. */
+#define PV_LENS_MAX_STACK 128
+
+/* Bytes of workspace pv_logit_lens needs for this shape (row means, answer sums, label logits, per-tile top partials). */
+size_t pv_logit_lens_workspace_bytes(int32_t n_rows, int32_t n_stack, int32_t d_model, int32_t n_answers);
+
+/* get_patch_logit_directions (prisma_tools/logit_lens.py:20-45: accumulated_resid, activation_cache.py:160-292, apply_ln_to_stack
+ * with the cached ln_final.hook_scale, :656-735, the einsum and the permute) and the per-cell argmax / rank of
+ * get_patch_logit_dictionary (logit_lens.py:73-88), in one pass over the taps: no stack copy, no normalised intermediate.
+ *   resid       HOST array of n_stack device pointers, tap s = [n_rows, d_model] of `dtype`, rows contiguous, 16-byte aligned
+ *   scale       [n_rows] fp32, ln_final.hook_scale of the row's token
+ *   answers     [n_answers, d_model] of `dtype`, 16-byte aligned
+ *   directions  [n_rows, n_stack, n_answers] fp32 = ((x_s[n] . a_o) - mean(x_s[n]) * sum(a_o)) / scale[n], or NULL
+ *   top_idx, top_logit  [n_rows, n_stack]: the largest logit of the row and the lowest column holding it (torch.argmax), each or NULL;
+ *               computed without writing the logits, top_logit bit-identical to that element of `directions`
+ *   rank        [n_rows, n_stack] int32 or NULL: columns that rank before column rank_of (a larger logit, or an equal one at a
+ *               lower index)
+ * A tap row that holds a NaN or an infinity is NaN in every column of `directions` (as in the reference, whose mean is not finite
+ * then); its top_idx is 0, its top_logit NaN, its rank -1.
+ * Returns PV_ERR_INVALID with the rule in pv_last_error for: dtype other than PV_DTYPE_BF16, d_model % 8 != 0,
+ * n_stack > PV_LENS_MAX_STACK, no output requested, rank without 0 <= rank_of < n_answers, a tap or the answers of 4 GiB or more;
+ * PV_ERR_WORKSPACE for a workspace below pv_logit_lens_workspace_bytes.  Allocates nothing. */
+int pv_logit_lens(int32_t dtype, const void* const* resid, int32_t n_stack, int32_t n_rows, int32_t d_model, const float* scale,
+                  const void* answers, int32_t n_answers, float* directions, int32_t* top_idx, float* top_logit, int32_t rank_of,
+                  int32_t* rank, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,8 +14,10 @@ from .vit import (Attention, Head, HookedViT, LayerNorm, LayerNormPre, MLP, Patc
                   TransformerBlock)
 from .sae_vit import HookedSAEViT
 from .text import HookedTextTransformer
+from . import logit_lens
 
 __all__ = [
+    "logit_lens",
     "ActivationCache", "HookedViTConfig", "HookPoint", "LensHandle", "HookedRootModule", "HookedViT", "HookedSAEViT",
     "HookedTextTransformer", "HookedTextTransformerConfig",
     "Attention", "Head", "LayerNorm", "LayerNormPre", "MLP", "PatchEmbedding", "PosEmbedding",

@@ -131,6 +131,7 @@ EXPORTS = [
     "pv_sae_dense_step", "pv_sae_topk_ghost", "pv_sae_relu_step", "pv_sae_relu_workspace_bytes", "pv_debug_sae_relu_offset", "pv_sae_ghost_workspace_bytes", "pv_sae_transcoder_scratch_bytes", "pv_sae_gated_scratch_bytes", "pv_sae_gated_step", "pv_sae_gated_sparse_workspace_bytes", "pv_sae_gated_step_sparse", "pv_sae_gated_topk_scratch_bytes", "pv_sae_gated_topk_step",
     "pv_debug_gemm_trace_arm", "pv_debug_gemm_trace_read", "pv_debug_set_tuning", "pv_debug_get_tuning",
     "pv_clip_preprocess",
+    "pv_logit_lens_workspace_bytes", "pv_logit_lens",
 ]
 
 
@@ -185,6 +186,9 @@ def lib() -> C.CDLL:
                                C.POINTER(C.c_double)]
     L.pv_debug_set_tuning.argtypes = [C.c_char_p, i32]
     L.pv_debug_get_tuning.argtypes = [C.c_char_p, C.POINTER(i32)]
+    L.pv_logit_lens_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.pv_logit_lens_workspace_bytes.restype = sz
+    L.pv_logit_lens.argtypes = [i32, C.POINTER(vp), i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, sz, vp]
     if hasattr(L, "pv_sae_plan_create"):
         L.pv_sae_plan_create.argtypes = [C.POINTER(SaeDesc), C.POINTER(vp)]
         L.pv_sae_plan_destroy.argtypes = [vp]

@@ -7,7 +7,7 @@
 
 Registers ``sys.modules`` aliases for the reference's import paths that sit on the hot path
 (/root/reference/src/vit_prisma/{models/base_vit (HookedViT, HookedSAEViT), models/base_text_transformer (HookedTextTransformer), configs/HookedTextTransformerConfig, models/model_loader (offline form), models/layers/*, configs/HookedViTConfig,
-prisma_tools/{hook_point, hooked_root_module, activation_cache, lens_handle}, sae/{config, sae,
+prisma_tools/{hook_point, hooked_root_module, activation_cache, lens_handle, logit_lens}, sae/{config, sae,
 train_sae}, sae/training/{activations_store, geometric_median, get_scheduler}}.py).  Reference SAE
 checkpoints pickle ``vit_prisma.sae.config.VisionModelSAERunnerConfig`` inside the ``.pt``
 (sae.py:299-320): with the alias in place ``torch.load`` resolves it to this package's class, so
@@ -45,7 +45,7 @@ def install_as(name: str = "vit_prisma", force: bool = False) -> None:
     if existing is not None and not getattr(existing, "_pv_alias", False) and not force:
         raise RuntimeError(f"a real '{name}' package is already imported; pass force=True to shadow it")
     import vit_prisma_amd as A
-    from . import activation_cache, configs, hook_points, hooked_root_module, model_loader, text, utils as U, vit
+    from . import activation_cache, configs, hook_points, hooked_root_module, logit_lens, model_loader, text, utils as U, vit
     from .sae import config as sae_config, geometric_median, get_scheduler, sae as sae_mod, store, trainer, variants
 
     layers = dict(
@@ -68,6 +68,8 @@ def install_as(name: str = "vit_prisma", force: bool = False) -> None:
         "prisma_tools.lens_handle": (False, _public(hook_points, ["LensHandle"])),
         "prisma_tools.hooked_root_module": (False, _public(hooked_root_module)),
         "prisma_tools.activation_cache": (False, _public(activation_cache)),
+        "prisma_tools.logit_lens": (False, _public(logit_lens, ["get_patch_logit_directions", "get_patch_logit_dictionary",
+                                                                "patch_logit_top", "patch_logit_dictionary", "use_native"])),
         "utils": (True, {}),
         "utils.prisma_utils": (False, _public(U)),
         "sae": (True, {**_public(A.sae, A.sae.__all__)}),
