@@ -635,7 +635,7 @@ int pv_sae_gated_step(pv_sae_plan* plan, pv_sae_state* st, const float* x, int32
  * its k-dependent buffers hold both lists) and out->topk_idx / topk_val hold 2 n_tokens x k entries: rows [0, n_tokens) = the
  * magnitude list (feature_acts), rows [n_tokens, 2 n_tokens) = the gate list (relu'd gate activations).  flags, scalars (4 = 0),
  * batch_mean / n_global and the follow-up calls as pv_sae_gated_step; scratch: pv_sae_gated_topk_scratch_bytes (gt.scratch is not
- * used). */
+ * used).  (sae_gated_topk.hip) */
 size_t pv_sae_gated_topk_scratch_bytes(const pv_sae_plan* plan, int32_t n_tokens);
 int pv_sae_gated_topk_step(pv_sae_plan* plan, pv_sae_state* st, const float* x, int32_t n_tokens, const float* batch_mean,
                            int32_t n_global, int32_t flags, pv_sae_out* out, void* workspace, size_t workspace_bytes, void* scratch,

@@ -122,7 +122,7 @@ def v4_of(d):
 
 
 def dpl_of(d):
-    """DPL_DISPATCH of csrc/sae.hip"""
+    """DPL_DISPATCH of csrc/sae_apply.hip"""
     return 4 if d <= 256 else 12 if d <= 768 else 16 if d <= 1024 else 20
 
 
@@ -595,7 +595,7 @@ def _lane_dot(a, b, V4):
 
 
 def twin(c, slip=None, lazy=False, fold=1):
-    """pv_sae_apply in float32 as csrc/sae.hip runs it.  lazy: the row form of the encoder (adam_wenct_kernel, W_enc == NULL: the parameter
+    """pv_sae_apply in float32 as csrc/sae_apply.hip runs it.  lazy: the row form of the encoder (adam_wenct_kernel, W_enc == NULL: the parameter
     layout is left as it was); fold: the bias vectors ride in that launch (the same blocks either way).  -> what ``check`` takes, with the
     ``_before`` arrays as a fresh engine's sync_shadows leaves them."""
     assert slip is None or slip in SLIPS, slip

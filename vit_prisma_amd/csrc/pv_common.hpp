@@ -192,6 +192,15 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// the sum over a 256-thread workgroup, on every thread (red: 4 floats of LDS; waves added in wave order)
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+    v = wave_sum(v);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
 
 // erf by Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7): 1 v_exp + 1 v_rcp + 6 FMA instead of ocml's
 // erff (~35 VALU); used where the result is rounded to bf16 anyway (2^-9 relative)

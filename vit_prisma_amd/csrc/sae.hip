@@ -17,7 +17,10 @@
 //               (rows of both gradients are written coalesced; W_enc's gradient is kept TRANSPOSED,
 //               [d_sae][d_in], and transposed back tile-wise inside the Adam kernel)
 //   bias grads  gb_dec = colsum(dY) - W_enc @ gb_enc   (the encoder-input path of b_dec, folded into a GEMV)
-//   apply       clip coefficient -> remove component parallel to decoder rows -> Adam, fused per tensor
+//   apply       clip coefficient -> remove component parallel to decoder rows -> Adam, fused per tensor            (sae_apply.hip)
+// Here: the pre-pass, the exact top-k, the decode kernel (sae_decode), column sums and reductions, the bias gradients (sae_gbdec), the
+// plan and its workspace, the transcoder helpers, pv_sae_encode_topk, pv_sae_forward, sae_sparse_tail and pv_sae_step.  The step cut at
+// the reconstruction for feature-parallel training: sae_tp.hip; the top-k form of the gated SAE: sae_gated_topk.hip.
 #include <math.h>
 #include <string.h>
 
@@ -25,20 +28,9 @@
 
 namespace {
 
-constexpr int MAXK = PV_SAE_MAXK;
-
 // ------------------------------------------------------------------------------------------------
 // generic helpers
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // column sums of a [rows][d] fp32 matrix (deterministic two-stage reduction).  stage 1: colsum_partial_body (sae_bwd.hpp: also a role
 // of csr_post_fill_kernel)
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ x, float* __restrict__ partial,
@@ -302,42 +294,8 @@ __device__ void sae_topk_row(const float* __restrict__ hidden, int32_t* __restri
 // ------------------------------------------------------------------------------------------------
 // A wave owns a token; lane l owns the 16-byte column groups 4 l + 256 i (i < V4: d_in <= 256 V4), so every gathered
 // W_dec row is fetched as V4 16-byte loads per lane (1 KiB per wave-instruction), four rows in flight (ld4, dot4: sae_bwd.hpp).
-// The CSR scan that rides in this launch as one more workgroup: ScanRole / scan_body_256 (sae_bwd.hpp).
-// The optimizer state (both Adam moments, 302 MB) and the gradients are touched ONCE per step: streamed past the caches
-// (nontemporal), so that what the next step gathers by row -- W_dec, W_enc^T and its fp16 copy, 188 MB, written by the same
-// kernels -- is what stays in the 256 MB MALL.  -DPV_NO_NT (A/B builds): plain accesses.
-typedef float pv_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4_stream(const float* p, bool ok) {
-#ifdef PV_NO_NT
-    return ld4(p, ok);
-#else
-    if (!ok) return make_float4(0.f, 0.f, 0.f, 0.f);
-    const pv_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const pv_f32x4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-#endif
-}
-__device__ __forceinline__ float ld1_stream(const float* p) {
-#ifdef PV_NO_NT
-    return *p;
-#else
-    return __builtin_nontemporal_load(p);
-#endif
-}
-__device__ __forceinline__ void st1_stream(float* p, float v) {
-#ifdef PV_NO_NT
-    *p = v;
-#else
-    __builtin_nontemporal_store(v, p);
-#endif
-}
-__device__ __forceinline__ void st4_stream(float* p, const float4& v) {
-#ifdef PV_NO_NT
-    *reinterpret_cast<float4*>(p) = v;
-#else
-    __builtin_nontemporal_store(pv_f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<pv_f32x4*>(p));
-#endif
-}
-
+// The CSR scan that rides in this launch as one more workgroup: ScanRole / scan_body_256 (sae_bwd.hpp).  Launched by sae_decode (below)
+// alone; what each parameter means to a caller: the fields of SaeDecode (sae_bwd.hpp).
 // MODE 0: the whole thing.  The feature-parallel step cuts it at the reconstruction: MODE 1 = this rank's PARTIAL
 // reconstruction sum_s val_s W_dec[idx_s] only (written to sae_out, no b_dec, no LN-out); MODE 2 = everything behind it, the
 // reconstruction summed over the ranks coming in through pre_sum.
@@ -358,12 +316,6 @@ __global__ __launch_bounds__(256) void sae_decode_kernel(
         scan_body_256(scan);
         return;
     }
-    // the sparse form of the ReLU + L1 step (pv_sae_relu_step): k = the per-token capacity, tok_cnt[n] = the pairs token n holds
-    // (front-packed; the rest of the row are holes), dh_add = l1_coefficient / N_global (the L1 term's gradient on every kept
-    // activation, sae.py:617-626), gate: the step's mode word -- nonzero = the step runs on the dense GEMMs, leave at once
-    // transcoder (pv_sae_state.tc): x = the TARGET, b_dec = b_dec_out, addend = the skip term x_in @ W_skip^T or nullptr
-    // inv_norm != nullptr: set_decoder_norm_to_unit_norm is pending -- W_dec still holds the un-normalised rows and row j
-    // stands for W_dec[j] * inv_norm[j] (the Adam kernel writes the normalised + updated row; see pv_sae_step)
     const int lane = threadIdx.x & 63;
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= n_tok) return;
@@ -501,27 +453,6 @@ __global__ __launch_bounds__(256) void reduce_sum_kernel(const float* __restrict
     }
 }
 
-// clip norm from the per-feature terms of the backward (+ gb_dec): one workgroup, fixed summation order
-__global__ __launch_bounds__(1024) void sqnorm_rowsq_kernel(const float* __restrict__ rowsq, int d_sae, const float* __restrict__ gb_dec,
-                                                            int d_in, float* __restrict__ scalars, const float* __restrict__ extra0,
-                                                            int n0, const float* __restrict__ extra1, int n1) {
-    __shared__ float red[16];
-    float s = 0.f;
-#pragma unroll 8
-    for (int j = threadIdx.x; j < d_sae; j += 1024) s += rowsq[j];             // (8 loads in flight; the sum in order)
-    for (int i = threadIdx.x; i < d_in; i += 1024) s += gb_dec[i] * gb_dec[i];
-    for (int i = threadIdx.x; i < n0; i += 1024) s += extra0[i] * extra0[i];          // transcoder: gb_dec_out, gW_skip
-    for (int i = threadIdx.x; i < n1; i += 1024) s += extra1[i] * extra1[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < 16; ++w) t += red[w];
-        scalars[3] = t;
-    }
-}
-
 // The step's last launch with the clip norm in it (PV_SAE_FUSED_SQNORM).  Workgroup b of the nb that finish gb_dec (64 columns each)
 // also takes block b of the clip norm: the squares of its own 64 columns + the b-th of nb slices of the backward's per-feature terms
 // (rowsq) -> sqpart[b]; the workgroup that finishes LAST (a ticket from an agent-scope acq_rel counter; the partials travel as
@@ -655,300 +586,6 @@ __global__ __launch_bounds__(256) void sae_gbdec_partial_kernel(const float* __r
     gbdec_partial_body(blockIdx.x, W_encT, gb_enc, partial, d_sae, d);
 }
 
-// ------------------------------------------------------------------------------------------------
-// gradient square-norm (two stage, deterministic)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ partial) {
-    __shared__ float red[4];
-    float s = 0.f;
-    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 1024) {
-        if (i + 3 < n) {
-            const float4 v = *reinterpret_cast<const float4*>(g + i);
-            s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        } else {
-            for (int64_t t = i; t < n; ++t) s += g[t] * g[t];
-        }
-    }
-    s = block_sum_256(s, red);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-
-// ------------------------------------------------------------------------------------------------
-// apply: clip -> project -> Adam  (train_sae.py:394-401; sae.py:279-297; torch.optim.Adam defaults)
-// ------------------------------------------------------------------------------------------------
-struct AdamC {
-    float lr, b1, b2, eps, bc1, bc2_sqrt, max_norm;
-};
-__device__ __forceinline__ float clip_coef(const float* scalars, float max_norm) {
-    if (max_norm <= 0.f) return 1.f;
-    const float total = sqrtf(scalars[3]);
-    return fminf(max_norm / (total + 1e-6f), 1.f);          // clip_grad_norm_: clamp(max_norm/(norm+1e-6), max=1)
-}
-__device__ __forceinline__ float adam_update(float w, float g, float& m, float& v, const AdamC& c) {
-    m = m + (g - m) * (1.f - c.b1);                         // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * c.b2 + (1.f - c.b2) * g * g;                    // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1-beta2)
-    const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
-    return w - (c.lr / c.bc1) * (m / denom);
-}
-
-// two vectors in one launch (b_enc's feature range and b_dec): blocks [0, nb0) take the first
-struct AdamVec2 {
-    float* W0; const float* G0; float* M0; float* V0; int lo0, hi0, nb0;
-    float* W1; const float* G1; float* M1; float* V1; int hi1;
-};
-__device__ __forceinline__ void adam_vec2_body(int bid, const AdamVec2& a, const float* __restrict__ scalars, const AdamC& c) {
-    const bool first = bid < a.nb0;
-    const int i = first ? a.lo0 + bid * 256 + threadIdx.x : (bid - a.nb0) * 256 + threadIdx.x;
-    if (i >= (first ? a.hi0 : a.hi1)) return;
-    float* W = first ? a.W0 : a.W1;
-    const float* G = first ? a.G0 : a.G1;
-    float* M = first ? a.M0 : a.M1;
-    float* V = first ? a.V0 : a.V1;
-    const float coef = clip_coef(scalars, c.max_norm);
-    float m = M[i], v = V[i];
-    W[i] = adam_update(W[i], G[i] * coef, m, v, c);
-    M[i] = m;
-    V[i] = v;
-}
-__global__ __launch_bounds__(256) void adam_vec2_kernel(const AdamVec2 a, const float* __restrict__ scalars, AdamC c) {
-    adam_vec2_body(blockIdx.x, a, scalars, c);
-}
-
-template <int V4>   // W_dec rows [j_lo, j_hi): one wave per row (16 bytes per lane and load), with the parallel-gradient projection
-__global__ __launch_bounds__(256) void adam_wdec_kernel(float* __restrict__ W, const float* __restrict__ G,
-                                                        float* __restrict__ M, float* __restrict__ V,
-                                                        const float* __restrict__ scalars, AdamC c, int j_lo, int j_hi, int d,
-                                                        const float* inv_norm, float* inv_next /* may be the same array */,
-                                                        const uint32_t* __restrict__ live_offs) {
-    const int lane = threadIdx.x & 63;
-    const int j = j_lo + blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= j_hi) return;
-    const bool live = !live_offs || live_offs[j + 1] != live_offs[j];        // (wave-uniform) PV_SAE_SPARSE_GRADS: no pair, g = 0
-    const float coef = clip_coef(scalars, c.max_norm);
-    const float rn = inv_norm ? inv_norm[j] : 1.f;            // pending set_decoder_norm_to_unit_norm (see pv_sae_step)
-    float4 w[V4], g[V4], m[V4], v[V4];
-    bool ok[V4];
-    float dot = 0.f;
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-        const int col = 4 * lane + 256 * i;
-        ok[i] = col < d;
-        const int64_t o = (int64_t)j * d + col;
-        w[i] = ld4(W + o, ok[i]);
-        g[i] = ld4_stream(G + o, ok[i] && live);
-        m[i] = ld4_stream(M + o, ok[i]);
-        v[i] = ld4_stream(V + o, ok[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-        w[i].x *= rn; w[i].y *= rn; w[i].z *= rn; w[i].w *= rn;
-        g[i].x *= coef; g[i].y *= coef; g[i].z *= coef; g[i].w *= coef;
-        dot += g[i].x * w[i].x + g[i].y * w[i].y + g[i].z * w[i].z + g[i].w * w[i].w;
-    }
-    dot = wave_sum(dot);
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-        if (!ok[i]) continue;
-        const int64_t o = (int64_t)j * d + 4 * lane + 256 * i;
-        float4 wn;                                          // g - dot * w: remove_gradient_parallel_to_decoder_directions
-        wn.x = adam_update(w[i].x, g[i].x - dot * w[i].x, m[i].x, v[i].x, c);
-        wn.y = adam_update(w[i].y, g[i].y - dot * w[i].y, m[i].y, v[i].y, c);
-        wn.z = adam_update(w[i].z, g[i].z - dot * w[i].z, m[i].z, v[i].z, c);
-        wn.w = adam_update(w[i].w, g[i].w - dot * w[i].w, m[i].w, v[i].w, c);
-        *reinterpret_cast<float4*>(W + o) = wn;
-        st4_stream(M + o, m[i]);
-        st4_stream(V + o, v[i]);
-        sq += wn.x * wn.x + wn.y * wn.y + wn.z * wn.z + wn.w * wn.w;
-    }
-    // the next step's set_decoder_norm_to_unit_norm needs 1 / ||row|| of what was just written: leave it behind
-    // (PV_SAE_INV_NORM_VALID) instead of re-reading W_dec for it
-    if (inv_next) {
-        sq = wave_sum(sq);
-        if (lane == 0) inv_next[j] = 1.0f / sqrtf(sq);
-    }
-}
-
-// W_enc's Adam step when the parameter's own [d_in][d_sae] layout is NOT rewritten (lazy materialisation, pv_sae_state.W_enc ==
-// NULL): everything lives in the transposed domain -- the fp32 master WT, gradient, moments, the fp16 shadow and the column
-// norms are all [d_sae][d_in] rows -- so this is the row-streaming form of adam_wdec_kernel (a wave per feature row, 16 bytes
-// per lane and load, no LDS transposes) instead of the 32 x 64 tile walk of wenc_rows_kernel.  Same arithmetic per element.
-template <int V4>
-__global__ __launch_bounds__(256) void adam_wenct_kernel(float* __restrict__ WT, _Float16* __restrict__ W16T, float* __restrict__ colsq,
-                                                         const float* __restrict__ GT, float* __restrict__ MT, float* __restrict__ VT,
-                                                         const float* __restrict__ scalars, AdamC c, int j_lo, int j_hi, int d,
-                                                         const uint32_t* __restrict__ live_offs, int nb_rows, const AdamVec2 v2) {
-    // workgroups beyond nb_rows (v2.nb0 + the blocks of b_dec of them): the two bias vectors' Adam (adam_vec2_body) -- it was a launch
-    if ((int)blockIdx.x >= nb_rows) {
-        adam_vec2_body(blockIdx.x - nb_rows, v2, scalars, c);
-        return;
-    }
-    const int lane = threadIdx.x & 63;
-    const int j = j_lo + blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= j_hi) return;
-    const bool live = !live_offs || live_offs[j + 1] != live_offs[j];        // (wave-uniform) PV_SAE_SPARSE_GRADS: no pair, g = 0
-    const float coef = clip_coef(scalars, c.max_norm);
-    float4 w[V4], g[V4], m[V4], v[V4];
-    bool ok[V4];
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-        const int col = 4 * lane + 256 * i;
-        ok[i] = col < d;
-        const int64_t o = (int64_t)j * d + col;
-        w[i] = ld4(WT + o, ok[i]);
-        g[i] = ld4_stream(GT + o, ok[i] && live);
-        m[i] = ld4_stream(MT + o, ok[i]);
-        v[i] = ld4_stream(VT + o, ok[i]);
-    }
-    float sq = 0.f;
-    bool big = false;
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-        if (!ok[i]) continue;
-        const int64_t o = (int64_t)j * d + 4 * lane + 256 * i;
-        float4 wn;
-        wn.x = adam_update(w[i].x, g[i].x * coef, m[i].x, v[i].x, c);
-        wn.y = adam_update(w[i].y, g[i].y * coef, m[i].y, v[i].y, c);
-        wn.z = adam_update(w[i].z, g[i].z * coef, m[i].z, v[i].z, c);
-        wn.w = adam_update(w[i].w, g[i].w * coef, m[i].w, v[i].w, c);
-        *reinterpret_cast<float4*>(WT + o) = wn;
-        st4_stream(MT + o, m[i]);
-        st4_stream(VT + o, v[i]);
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-        const h4 hv = {(_Float16)wn.x, (_Float16)wn.y, (_Float16)wn.z, (_Float16)wn.w};
-        *reinterpret_cast<h4*>(W16T + o) = hv;
-        sq += wn.x * wn.x + wn.y * wn.y + wn.z * wn.z + wn.w * wn.w;
-        big = big || !(fabsf(wn.x) <= 6.0e4f) || !(fabsf(wn.y) <= 6.0e4f) || !(fabsf(wn.z) <= 6.0e4f) || !(fabsf(wn.w) <= 6.0e4f);
-    }
-    sq = wave_sum(sq);
-    const bool any_big = __any(big);                        // outside the fp16 range (or NaN): the filter must not be trusted
-    if (lane == 0) colsq[j] = any_big ? INFINITY : sq;
-}
-
-// ------------------------------------------------------------------------------------------------
-// W_enc lives three times: the module's parameter W [d_in][d_sae]; WT = its transpose [d_sae][d_in] in fp32 -- the
-// layout the sparse backward writes gradients in and the exact re-scoring of sae_enc.hip gathers rows from, hence
-// the layout Adam runs in (gradient, both moments and WT are read and written coalesced, feature rows [j_lo, j_hi) are
-// contiguous: the data-parallel trainer shards the optimizer by feature); and W16T = WT rounded to fp16, the B operand of
-// the filter GEMM.  One workgroup owns 32 features x all d_in: tile-wise it updates WT / moments / W16T in place,
-// transposes the new values through LDS into W, and leaves ||W_enc[:, j]||^2 (the filter's error bound) in colsq.
-// MODE 0: Adam step.  MODE 1: rebuild W, W16T, colsq from WT (after an all-gather of WT).  MODE 2: rebuild WT, W16T,
-// colsq from W (parameters edited from outside).
-// ------------------------------------------------------------------------------------------------
-template <int MODE>
-__global__ __launch_bounds__(256) void wenc_rows_kernel(float* __restrict__ W, float* __restrict__ WT, _Float16* __restrict__ W16T,
-                                                        float* __restrict__ colsq, const float* __restrict__ GT,
-                                                        float* __restrict__ MT, float* __restrict__ VT,
-                                                        const float* __restrict__ scalars, AdamC c, int d_in, int d_sae,
-                                                        int j_lo, int j_hi, const uint32_t* __restrict__ live_offs = nullptr) {
-    constexpr int NC = 2;                                     // 32-column chunks per iteration (16 independent loads per array)
-    __shared__ float tile[NC][32][33];
-    const int j0 = j_lo + blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    float coef = 1.f;
-    if constexpr (MODE == 0) coef = clip_coef(scalars, c.max_norm);
-    float sq[4] = {0.f, 0.f, 0.f, 0.f};
-    bool big = false;
-    bool live[4] = {true, true, true, true};                  // PV_SAE_SPARSE_GRADS: rows of features without a pair are not read
-    if constexpr (MODE == 0) {
-        if (live_offs) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int j = j0 + ty + 8 * r;
-                live[r] = j < j_hi && live_offs[j + 1] != live_offs[j];
-            }
-        }
-    }
-    for (int i0 = 0; i0 < d_in; i0 += 32 * NC) {
-        if constexpr (MODE == 2) {
-#pragma unroll
-            for (int u = 0; u < NC; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {                   // read W[i][j0 + tx] coalesced along j
-                    const int i = i0 + 32 * u + ty + 8 * r, j = j0 + tx;
-                    tile[u][tx][ty + 8 * r] = (i < d_in && j < j_hi) ? W[(int64_t)i * d_sae + j] : 0.f;
-                }
-            __syncthreads();
-        }
-        float wv[NC][4], gv[NC][4], mv[NC][4], vv[NC][4];
-        if constexpr (MODE == 0) {
-#pragma unroll
-            for (int u = 0; u < NC; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = j0 + ty + 8 * r, i = i0 + 32 * u + tx;
-                    const bool in = j < j_hi && i < d_in;
-                    const int64_t o = (int64_t)j * d_in + i;
-                    wv[u][r] = in ? WT[o] : 0.f;
-                    gv[u][r] = (in && live[r]) ? ld1_stream(GT + o) : 0.f;      // (optimizer state and gradients: streamed, see ld4_stream)
-                    mv[u][r] = in ? ld1_stream(MT + o) : 0.f;
-                    vv[u][r] = in ? ld1_stream(VT + o) : 0.f;
-                }
-        }
-#pragma unroll
-        for (int u = 0; u < NC; ++u)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int j = j0 + ty + 8 * r, i = i0 + 32 * u + tx;
-                if (j < j_hi && i < d_in) {
-                    const int64_t o = (int64_t)j * d_in + i;
-                    float wn;
-                    if constexpr (MODE == 0) {
-                        float m = mv[u][r], v = vv[u][r];
-                        wn = adam_update(wv[u][r], gv[u][r] * coef, m, v, c);
-                        st1_stream(MT + o, m);
-                        st1_stream(VT + o, v);
-                        WT[o] = wn;
-                    } else if constexpr (MODE == 1) {
-                        wn = WT[o];
-                    } else {
-                        wn = tile[u][ty + 8 * r][tx];
-                        WT[o] = wn;
-                    }
-                    W16T[o] = (_Float16)wn;
-                    sq[r] += wn * wn;
-                    big = big || !(fabsf(wn) <= 6.0e4f);        // outside the fp16 range (or NaN): the filter must not be trusted
-                    if constexpr (MODE != 2) { if (W) tile[u][ty + 8 * r][tx] = wn; }
-                }
-            }
-        if constexpr (MODE != 2) {
-            if (W) {                                                   // (uniform) W == nullptr: the parameter layout is materialised lazily
-                __syncthreads();
-#pragma unroll
-                for (int u = 0; u < NC; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int i = i0 + 32 * u + ty + 8 * r, j = j0 + tx;
-                        if (i < d_in && j < j_hi) W[(int64_t)i * d_sae + j] = tile[u][tx][ty + 8 * r];
-                    }
-                __syncthreads();
-            }
-        } else {
-            __syncthreads();
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float s = big ? INFINITY : sq[r];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);           // the 32 lanes that share ty
-        const int j = j0 + ty + 8 * r;
-        if (tx == 0 && j < j_hi) colsq[j] = s;
-    }
-}
-
-__global__ __launch_bounds__(256) void adam_vec_kernel(float* __restrict__ W, const float* __restrict__ G,
-                                                       float* __restrict__ M, float* __restrict__ V,
-                                                       const float* __restrict__ scalars, AdamC c, int lo, int hi) {
-    const int i = lo + blockIdx.x * 256 + threadIdx.x;
-    if (i >= hi) return;
-    const float coef = clip_coef(scalars, c.max_norm);
-    float m = M[i], v = V[i];
-    W[i] = adam_update(W[i], G[i] * coef, m, v, c);
-    M[i] = m;
-    V[i] = v;
-}
-
 // 1 / ||W_dec[j]|| (the read-only half of set_decoder_norm_to_unit_norm): a wave takes four rows, all loads in flight
 __global__ __launch_bounds__(256) void dec_inv_norm_kernel(const float* __restrict__ W, float* __restrict__ inv, int rows, int d) {
     const int lane = threadIdx.x & 63;
@@ -972,34 +609,33 @@ __global__ __launch_bounds__(256) void dec_inv_norm_kernel(const float* __restri
     }
 }
 
-// set_decoder_norm_to_unit_norm (sae.py:275-277)
-template <int DPL>
-__global__ __launch_bounds__(256) void renorm_rows_kernel(float* __restrict__ W, int rows, int d) {
-    const int lane = threadIdx.x & 63;
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= rows) return;
-    float w[DPL];
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) {
-        const int c = lane + 64 * i;
-        w[i] = c < d ? W[(int64_t)j * d + c] : 0.f;
-        sq += w[i] * w[i];
-    }
-    const float nrm = sqrtf(wave_sum(sq));
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) {
-        const int c = lane + 64 * i;
-        if (c < d) W[(int64_t)j * d + c] = w[i] / nrm;
-    }
-}
-
 }  // namespace
 
 void sae_topk_rows(const float* hidden, int32_t* idx_out, float* val_out, int d_sae, int k, int n_rows, const int32_t* row_list,
                    const uint32_t* n_list, int slots, uint32_t* feat_cnt, uint32_t* wpos, hipStream_t stream) {
     hipLaunchKernelGGL(sae_topk_kernel, dim3(row_list ? slots : n_rows), dim3(256), 0, stream, hidden, idx_out, val_out, d_sae, k,
                        row_list, n_list, feat_cnt, wpos);
+}
+
+// The one launch site of sae_decode_kernel: a token per wave, + the workgroup of the folded CSR scan when a.scan is set
+int sae_decode(const SaeDecode& a, hipStream_t stream) {
+    const bool scan = a.mode != 1 && a.scan.cnt;
+    const dim3 grid((a.N + 3) / 4 + (scan ? 1 : 0)), block(256);
+#define DECODE(D, MODE)                                                                                                              \
+    hipLaunchKernelGGL((sae_decode_kernel<D, MODE>), grid, block, 0, stream, a.x, a.W_dec, a.b_dec, a.idx, a.val, a.mu, a.sd, a.norm, \
+                       a.sae_out, a.dY, a.dh, a.loss_part, a.N, a.d, a.k, a.grad_scale, a.dY ? 1 : 0, a.inv_norm, a.pre_sum, a.addend, \
+                       a.dh_add, a.tok_cnt, a.gate, a.scan)
+#define CALL(D)                                  \
+    do {                                         \
+        if (a.mode == 0) DECODE(D, 0);           \
+        else if (a.mode == 1) DECODE(D, 1);      \
+        else DECODE(D, 2);                       \
+    } while (0)
+    V4_DISPATCH(a.d, CALL);
+#undef CALL
+#undef DECODE
+    PV_LAUNCH_CHECK("sae_decode_kernel");
+    return PV_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1123,49 +759,6 @@ extern "C" size_t pv_debug_sae_ws_offset(const pv_sae_plan* plan, const char* na
     return (size_t)-1;
 }
 
-#define DPL_DISPATCH(d_in, CALL)            \
-    do {                                    \
-        if ((d_in) <= 64 * 4) { CALL(4); }  \
-        else if ((d_in) <= 64 * 12) { CALL(12); } \
-        else if ((d_in) <= 64 * 16) { CALL(16); } \
-        else { CALL(20); }                  \
-    } while (0)
-
-extern "C" int pv_sae_renorm_decoder(pv_sae_plan* plan, pv_sae_state* st, void* stream_) {
-    PV_REQUIRE(plan && st && st->W_dec, "null argument");
-    hipStream_t stream = (hipStream_t)stream_;
-    const pv_sae_desc& d = plan->d;
-    const dim3 grid((d.d_sae + 3) / 4), block(256);
-#define CALL(D) hipLaunchKernelGGL((renorm_rows_kernel<D>), grid, block, 0, stream, st->W_dec, d.d_sae, d.d_in)
-    DPL_DISPATCH(d.d_in, CALL);
-#undef CALL
-    PV_LAUNCH_CHECK("renorm_rows_kernel");
-    plan->renorm_pending = false;
-    return PV_OK;
-}
-
-// Rebuild the encoder shadows for features [j_lo, j_hi).  from_transposed = 0: W_enc is the truth (parameters were edited
-// outside: load_state_dict, a fresh engine) -> W_encT, W_enc16T, enc_colsq; 1: W_encT is the truth (an all-gather of the
-// sharded optimizer's slices just landed) -> W_enc, W_enc16T, enc_colsq.
-extern "C" int pv_sae_sync_shadows(pv_sae_plan* plan, pv_sae_state* st, int32_t from_transposed, int32_t j_lo, int32_t j_hi,
-                                   void* stream_) {
-    PV_REQUIRE(plan && st && st->W_enc && st->W_encT && st->W_enc16T && st->enc_colsq, "null argument");
-    const pv_sae_desc& d = plan->d;
-    PV_REQUIRE(j_lo >= 0 && j_lo <= j_hi && j_hi <= d.d_sae, "feature range");
-    if (j_lo == j_hi) return PV_OK;
-    hipStream_t stream = (hipStream_t)stream_;
-    const dim3 grid((j_hi - j_lo + 31) / 32), block(256);
-    AdamC c = {};
-    if (from_transposed)
-        hipLaunchKernelGGL((wenc_rows_kernel<1>), grid, block, 0, stream, st->W_enc, st->W_encT, (_Float16*)st->W_enc16T, st->enc_colsq,
-                           (const float*)nullptr, (float*)nullptr, (float*)nullptr, (const float*)nullptr, c, d.d_in, d.d_sae, j_lo, j_hi);
-    else
-        hipLaunchKernelGGL((wenc_rows_kernel<2>), grid, block, 0, stream, st->W_enc, st->W_encT, (_Float16*)st->W_enc16T, st->enc_colsq,
-                           (const float*)nullptr, (float*)nullptr, (float*)nullptr, (const float*)nullptr, c, d.d_in, d.d_sae, j_lo, j_hi);
-    PV_LAUNCH_CHECK("wenc_rows_kernel");
-    return PV_OK;
-}
-
 // ---- transcoder (pv_sae_state.tc; sae/transcoder.py:6-116) ----------------------------------------------------------------
 // loss normaliser of the target: ||y_n - mean_n(y)||_2 (sae.py:145-147 as called by transcoder.py:78).  One wave per token.
 // d_true < d (a transcoder whose output is narrower than its input, pv_sae_transcoder.d_out_true: rows padded to the common width d):
@@ -1262,38 +855,29 @@ int sae_prep(const pv_sae_desc& d, const float* x, const float* b_dec, const flo
     return PV_OK;
 }
 
-// gb_dec = colsum(dY) - W_enc @ gb_enc (the encoder-input path of b_dec): both terms as partial rows of one column sum
-// have_colsum: the partial column sums of dY are in ws.colpart already (csr_post_fill_kernel)
+// The bias gradients behind every step: colsum(dY) and the encoder-input path of b_dec, -W_enc @ gb_enc, both as partial rows of a column
+// sum (ws.colpart: nblk rows of dY partials, under them the ngb rows of sae_gbdec_partial_kernel).  dy_to: which parameter colsum(dY)
+// belongs to (SaeDyTo, sae.hpp).  have_colsum: the partial column sums of dY are in ws.colpart already (csr_post_fill_kernel).
 int sae_gbdec(const pv_sae_desc& d, const pv_sae_state* st, const float* dY, int N, unsigned char* wsb, const SaeWs& ws,
-              hipStream_t stream, bool have_colsum, float* sq_scalars) {
+              hipStream_t stream, SaeDyTo dy_to, bool have_colsum, float* sq_scalars) {
     const int nblk = (N + CS_ROWS - 1) / CS_ROWS, ngb = (d.d_sae + GBD_ROWS - 1) / GBD_ROWS;
+    const dim3 grid_fin((d.d_in + 63) / 64), block_fin(1024);
     float* colpart = (float*)(wsb + ws.colpart);
+    float* encpart = colpart + (size_t)nblk * d.d_in;
     if (!have_colsum) hipLaunchKernelGGL(colsum_partial_kernel, dim3(nblk), dim3(256), 0, stream, dY, colpart, N, d.d_in);
     hipLaunchKernelGGL(sae_gbdec_partial_kernel, dim3(ngb), dim3(256), 0, stream, (const float*)st->W_encT, (const float*)st->gb_enc,
-                       colpart + (size_t)nblk * d.d_in, d.d_sae, d.d_in);
-    if (sq_scalars)                 // PV_SAE_FUSED_SQNORM: the clip norm out of the same launch (the ticket word: n_long[2], zeroed by the scan)
-        hipLaunchKernelGGL(colsum_final_sq_kernel, dim3((d.d_in + 63) / 64), dim3(1024), 0, stream, (const float*)colpart, st->gb_dec,
+                       encpart, d.d_sae, d.d_in);
+    if (dy_to == SAE_DY_TO_GB_DEC_OUT)
+        hipLaunchKernelGGL(colsum_final_kernel, grid_fin, block_fin, 0, stream, (const float*)colpart, st->tc.gb_dec_out, nblk, d.d_in, 1.0f);
+    if (dy_to != SAE_DY_TO_GB_DEC)  // the encoder term alone
+        hipLaunchKernelGGL(colsum_final_kernel, grid_fin, block_fin, 0, stream, (const float*)encpart, st->gb_dec, ngb, d.d_in, 1.0f);
+    else if (sq_scalars)            // PV_SAE_FUSED_SQNORM: the clip norm out of the same launch (the ticket word: n_long[2], zeroed by the scan)
+        hipLaunchKernelGGL(colsum_final_sq_kernel, grid_fin, block_fin, 0, stream, (const float*)colpart, st->gb_dec,
                            nblk + ngb, d.d_in, (const float*)(wsb + ws.rowsq), d.d_sae, (float*)(wsb + ws.sqpart),
                            (uint32_t*)(wsb + ws.n_long) + 2, sq_scalars);
     else
-        hipLaunchKernelGGL(colsum_final_kernel, dim3((d.d_in + 63) / 64), dim3(1024), 0, stream, (const float*)colpart, st->gb_dec,
-                           nblk + ngb, d.d_in, 1.0f);
+        hipLaunchKernelGGL(colsum_final_kernel, grid_fin, block_fin, 0, stream, (const float*)colpart, st->gb_dec, nblk + ngb, d.d_in, 1.0f);
     PV_LAUNCH_CHECK("sae bias-grad kernels");
-    return PV_OK;
-}
-
-int sae_tc_bias_grads(const pv_sae_desc& d, const pv_sae_state* st, const float* dY, int N, unsigned char* wsb, const SaeWs& ws,
-                      hipStream_t stream) {
-    const int nblk = (N + CS_ROWS - 1) / CS_ROWS, ngb = (d.d_sae + GBD_ROWS - 1) / GBD_ROWS;
-    float* colpart = (float*)(wsb + ws.colpart);
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(nblk), dim3(256), 0, stream, dY, colpart, N, d.d_in);
-    hipLaunchKernelGGL(sae_gbdec_partial_kernel, dim3(ngb), dim3(256), 0, stream, (const float*)st->W_encT, (const float*)st->gb_enc,
-                       colpart + (size_t)nblk * d.d_in, d.d_sae, d.d_in);
-    hipLaunchKernelGGL(colsum_final_kernel, dim3((d.d_in + 63) / 64), dim3(1024), 0, stream, (const float*)colpart, st->tc.gb_dec_out,
-                       nblk, d.d_in, 1.0f);
-    hipLaunchKernelGGL(colsum_final_kernel, dim3((d.d_in + 63) / 64), dim3(1024), 0, stream,
-                       (const float*)(colpart + (size_t)nblk * d.d_in), st->gb_dec, ngb, d.d_in, 1.0f);
-    PV_LAUNCH_CHECK("transcoder bias-grad kernels");
     return PV_OK;
 }
 
@@ -1312,11 +896,10 @@ void sae_reduce_sum(const float* v, float* out, int n, float scale, int slot, in
     hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, stream, v, out, n, scale, slot, slot2, gate, want);
 }
 
-// want_csr: also count the kept pairs per feature (ws.cnt) and record their positions (ws.wpos) for the backward
-// cnt_over / wpos_over: other destinations for those two (the top-k gated step encodes twice); skip_prep: sae_prep has already run on x
-static int sae_encode_topk(pv_sae_plan* plan, const pv_sae_state* st, const float* x, int N, const float* batch_mean,
-                           int32_t* topk_idx, float* topk_val, bool want_csr, unsigned char* wsb, const SaeWs& ws, hipStream_t stream,
-                           uint32_t* cnt_over = nullptr, uint32_t* wpos_over = nullptr, bool skip_prep = false) {
+// prep + encoder + top-k (the arguments: sae.hpp)
+int sae_encode_topk(pv_sae_plan* plan, const pv_sae_state* st, const float* x, int N, const float* batch_mean,
+                    int32_t* topk_idx, float* topk_val, bool want_csr, unsigned char* wsb, const SaeWs& ws, hipStream_t stream,
+                    uint32_t* cnt_over, uint32_t* wpos_over, bool skip_prep) {
     const pv_sae_desc& d = plan->d;
     uint32_t* feat_cnt = want_csr ? (cnt_over ? cnt_over : (uint32_t*)(wsb + ws.cnt)) : nullptr;
     uint32_t* wpos = want_csr ? (wpos_over ? wpos_over : (uint32_t*)(wsb + ws.wpos)) : nullptr;
@@ -1383,15 +966,12 @@ extern "C" int pv_sae_forward(pv_sae_plan* plan, const pv_sae_state* st, const f
     unsigned char* wsb = (unsigned char*)workspace;
     int rc = sae_encode_topk(plan, st, x, N, nullptr, topk_idx, topk_val, false, wsb, ws, stream);
     if (rc) return rc;
-    const dim3 grid((N + 3) / 4), block(256);
-#define CALL(D)                                                                                                      \
-    hipLaunchKernelGGL((sae_decode_kernel<D>), grid, block, 0, stream, x, (const float*)st->W_dec, (const float*)st->b_dec, \
-                       (const int32_t*)topk_idx, (const float*)topk_val, (const float*)(wsb + ws.mu),                \
-                       (const float*)(wsb + ws.sd), (const float*)(wsb + ws.norm), sae_out, (float*)nullptr, (float*)nullptr, \
-                       (float*)(wsb + ws.loss_part), N, d.d_in, d.k, 0.0f, 0, (const float*)nullptr)
-    V4_DISPATCH(d.d_in, CALL);
-#undef CALL
-    PV_LAUNCH_CHECK("sae_decode_kernel");
+    SaeDecode dec;                                                  // (no dY: decode, LN-out and the loss terms only)
+    dec.N = N; dec.d = d.d_in; dec.k = d.k; dec.x = x; dec.W_dec = st->W_dec; dec.b_dec = st->b_dec; dec.idx = topk_idx; dec.val = topk_val;
+    dec.mu = (const float*)(wsb + ws.mu); dec.sd = (const float*)(wsb + ws.sd); dec.norm = (const float*)(wsb + ws.norm);
+    dec.sae_out = sae_out; dec.loss_part = (float*)(wsb + ws.loss_part);
+    rc = sae_decode(dec, stream);
+    if (rc) return rc;
     if (scalars)
         hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, stream, (const float*)(wsb + ws.loss_part), scalars, N,
                            1.0f / ((float)N * (float)d.d_in), 1, -1);
@@ -1402,7 +982,7 @@ extern "C" int pv_sae_forward(pv_sae_plan* plan, const pv_sae_state* st, const f
 
 // Everything of the k-sparse step behind the selection: decode + LN-out + loss + dY + dh, the CSR by feature, the sparse backward,
 // the bias gradients.  Shared by pv_sae_step (k = the plan's k) and by the sparse form of the ReLU + L1 step (pv_sae_relu_step:
-// k = the per-token capacity, tok_cnt / dh_add / gate as described at sae_decode_kernel; the k-dependent buffers come in through tb).
+// k = the per-token capacity, tok_cnt / dh_add / gate as described at SaeDecode; the k-dependent buffers come in through tb).
 int sae_sparse_tail(pv_sae_plan* plan, pv_sae_state* st, const float* x, int N, int n_global, int k, const int32_t* topk_idx,
                     const float* topk_val, float* sae_out, float* scalars, float* fire_count, int update_stats, bool sparse,
                     const float* inv_norm, const SaeTail& tb, unsigned char* wsb, const SaeWs& ws, const float* y, const float* bdo,
@@ -1416,27 +996,20 @@ int sae_sparse_tail(pv_sae_plan* plan, pv_sae_state* st, const float* x, int N, 
     float* sae_in = (float*)(wsb + ws.sae_in);
     {
         ProfScope prof(PV_PROF_SAE_BWD, stream, 4.0 * n_pairs * (double)d.d_in * 2.0, 0.0);
-        const float grad_scale = 2.0f / ((float)n_global * (float)sae_loss_width(d, st));      // (a transcoder: the mean is over N x d_out)
         const float loss_scale = 1.0f / ((float)n_global * (float)sae_loss_width(d, st));
-        const dim3 grid((N + 3) / 4), block(256);
         // the CSR scan reads the selection's counts only -- it runs as one more workgroup of the decode launch (ScanRole).  (The sparse
         // form of the ReLU step on a batch that turns out dense: the scan walks counts nobody will use and writes scalars the dense
         // form overwrites -- as the scan's own launch did)
         const bool folded = g_pv_tuning.sae_fold != 0;
-        ScanRole scan = {};
-        if (folded) {
-            scan.cnt = (const uint32_t*)(wsb + ws.cnt); scan.offs = (uint32_t*)(wsb + ws.offs); scan.n_long = (uint32_t*)(wsb + ws.n_long);
-            scan.d_sae = d.d_sae; scan.scalars = scalars; scan.tokens = (float)N;
-        }
-        const dim3 grid_dec((N + 3) / 4 + (folded ? 1 : 0));
-#define CALL(D)                                                                                                      \
-    hipLaunchKernelGGL((sae_decode_kernel<D>), grid_dec, block, 0, stream, y, (const float*)st->W_dec, bdo,          \
-                       topk_idx, topk_val, (const float*)(wsb + ws.mu),      \
-                       (const float*)(wsb + ws.sd), (const float*)(wsb + ws.norm), sae_out, dY, dh,             \
-                       (float*)(wsb + ws.loss_part), N, d.d_in, k, grad_scale, 1, inv_norm, (const float*)nullptr, skip, dh_add, tok_cnt, gate, scan)
-        V4_DISPATCH(d.d_in, CALL);
-#undef CALL
-        PV_LAUNCH_CHECK("sae_decode_kernel");
+        SaeDecode dec;
+        dec.N = N; dec.d = d.d_in; dec.k = k; dec.x = y; dec.W_dec = st->W_dec; dec.b_dec = bdo; dec.idx = topk_idx; dec.val = topk_val;
+        dec.mu = (const float*)(wsb + ws.mu); dec.sd = (const float*)(wsb + ws.sd); dec.norm = (const float*)(wsb + ws.norm);
+        dec.sae_out = sae_out; dec.dY = dY; dec.dh = dh; dec.loss_part = (float*)(wsb + ws.loss_part);
+        dec.grad_scale = 2.0f / ((float)n_global * (float)sae_loss_width(d, st));      // (a transcoder: the mean is over N x d_out)
+        dec.inv_norm = inv_norm; dec.addend = skip; dec.dh_add = dh_add; dec.tok_cnt = tok_cnt; dec.gate = gate;
+        if (folded) dec.scan = sae_scan_role(d, wsb, ws, (const uint32_t*)(wsb + ws.cnt), scalars, N);
+        rc = sae_decode(dec, stream);
+        if (rc) return rc;
         const bool cs_here = bias_grads && !tc;
         SaeBwd b;
         b.N = N; b.k = k; b.idx = topk_idx; b.val = topk_val; b.dY = dY; b.sae_in = sae_in; b.scalars = scalars; b.tail = tb;
@@ -1447,317 +1020,13 @@ int sae_sparse_tail(pv_sae_plan* plan, pv_sae_state* st, const float* x, int N, 
         // gb_dec = colsum(dY) - W_enc @ gb_enc: both terms as partial rows of one column sum
         // (bias_grads false: pv_sae_relu_step runs them once, behind whichever of its two forms produced dY and gb_enc)
         if (bias_grads) {
-            rc = tc ? sae_tc_bias_grads(d, st, dY, N, wsb, ws, stream) : sae_gbdec(d, st, dY, N, wsb, ws, stream, cs_here, sq_scalars);
+            rc = sae_gbdec(d, st, dY, N, wsb, ws, stream, tc ? SAE_DY_TO_GB_DEC_OUT : SAE_DY_TO_GB_DEC, cs_here, sq_scalars);
             if (rc) return rc;
             if (tc) {
                 rc = sae_tc_skip_backward(d, st, x, dY, N, stream);
                 if (rc) return rc;
             }
         }
-    }
-    return PV_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The TOP-K form of the gated SAE (activation_fn_str = "topk" on a GatedSparseAutoencoder, sae.py:699-716, 741-745, 773-778):
-//     feature_acts = [gate_pre > 0] TopK(mag_pre),   mag_pre  = sae_in (W_enc e^r_mag) + b_mag
-//     pi_gate_act  = TopK(gate_pre),                 gate_pre = sae_in W_enc + b_gate
-//     loss = mse(feature_acts W_dec + b_dec) + aux(pi_gate_act W_dec + b_dec against sae_in);  no L1 term
-// Two k-sparse lists per token, so the step is the k-sparse machinery twice over:
-//   * the magnitude path's top-k runs on the SAME filtered encoder against a scaled copy of the encoder shadows (W_magT[j] = W_encT[j]
-//     e^r_j in fp32 and fp16, its column norms: one pass per step, gated_scale_rows_kernel), the gate path's on the shadows themselves
-//     with b_gate as the bias;
-//   * the gate of every kept magnitude is evaluated EXACTLY (gated_topk_mask_kernel: the fp32 dot product of the exact re-scoring);
-//   * decode once per list (sae_decode_kernel: the second against sae_in with constant LN-out terms), then ONE CSR + sparse backward
-//     over the two lists stacked as 2N "tokens" of k slots -- rows [0, N): {f, dY, dh = dM e^r}, rows [N, 2N): {g, dVia, dh = dG},
-//     sae_in repeated -- so that gW_dec, gW_enc^T and colsum(dP) (parked in gb_enc) come out of the unmodified backward kernels;
-//   * per-feature sums over the CSR lists: gb_mag, gr_mag, gb_gate, firing statistics.
-// The plan must be created for 2 x the tokens of a step (its k-dependent buffers hold both lists).
-// ------------------------------------------------------------------------------------------------
-namespace {
-struct GatedTopkWs {
-    size_t total, wmagT, wmag16, colsq, cnt_m, cnt2, dM, mu0, one, l0part, auxpart, tmpd, cspart;
-};
-GatedTopkWs gated_topk_carve(const pv_sae_desc& d, int n_tokens) {
-    GatedTopkWs w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (size_t)pv_align_up((int64_t)bytes, 256); return o; };
-    const size_t F = d.d_sae, D = d.d_in, N = n_tokens;
-    w.wmagT = take(F * D * 4);
-    w.wmag16 = take(F * D * 2);
-    w.colsq = take(F * 4);
-    w.cnt_m = take(F * 4);
-    w.cnt2 = take(F * 4);
-    w.dM = take(N * (size_t)d.k * 4);
-    w.mu0 = take(N * 4);
-    w.one = take(N * 4);
-    w.l0part = take(N * 4);
-    w.auxpart = take(N * 4);
-    w.tmpd = take(D * 4);
-    w.cspart = take((N / 16 + 2) * D * 4);
-    w.total = off + 256;
-    return w;
-}
-
-// W_magT[j] = W_encT[j] e^r_j (fp32 + fp16) and its squared column norm (INFINITY outside the fp16 range, as adam_wenct_kernel);
-// one wave per feature
-__global__ __launch_bounds__(256) void gated_scale_rows_kernel(const float* __restrict__ WT, const float* __restrict__ r_mag,
-                                                               float* __restrict__ MT, _Float16* __restrict__ M16T,
-                                                               float* __restrict__ colsq, int F, int d) {
-    const int lane = threadIdx.x & 63;
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= F) return;
-    const float e = expf(r_mag[j]);
-    float sq = 0.f;
-    bool big = false;
-    for (int c = 4 * lane; c < d; c += 256) {
-        float4 w = *reinterpret_cast<const float4*>(WT + (int64_t)j * d + c);
-        w.x *= e; w.y *= e; w.z *= e; w.w *= e;
-        *reinterpret_cast<float4*>(MT + (int64_t)j * d + c) = w;
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-        const h4 hv = {(_Float16)w.x, (_Float16)w.y, (_Float16)w.z, (_Float16)w.w};
-        *reinterpret_cast<h4*>(M16T + (int64_t)j * d + c) = hv;
-        sq += w.x * w.x + w.y * w.y + w.z * w.z + w.w * w.w;
-        big = big || !(fabsf(w.x) <= 6.0e4f) || !(fabsf(w.y) <= 6.0e4f) || !(fabsf(w.z) <= 6.0e4f) || !(fabsf(w.w) <= 6.0e4f);
-    }
-    sq = wave_sum(sq);
-    const bool any_big = __any(big);
-    if (lane == 0) colsq[j] = any_big ? INFINITY : sq;
-}
-
-// a wave per token: the gate of each kept magnitude, exactly (gate_pre = sae_in . W_encT[j] + b_gate[j] in the summation order of the
-// exact re-scoring), feature_acts = [gate_pre > 0] relu(top-k magnitude) written over the magnitude; the token's count of f > 0 (l0);
-// the constant LN-out terms of the pass through the gate
-template <int V4>
-__global__ __launch_bounds__(256) void gated_topk_mask_kernel(const float* __restrict__ sae_in, const float* __restrict__ W_encT,
-                                                              const float* __restrict__ b_gate, const int32_t* __restrict__ idx,
-                                                              float* __restrict__ val, float* __restrict__ l0part,
-                                                              float* __restrict__ mu0, float* __restrict__ one, int n_tok, int d, int k) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= n_tok) return;
-    bool ok[V4];
-    int col[V4];
-    float4 xr[V4];
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-        col[i] = 4 * lane + 256 * i;
-        ok[i] = col[i] < d;
-        xr[i] = ld4(sae_in + (int64_t)n * d + col[i], ok[i]);
-    }
-    float cnt = 0.f;
-    for (int s = 0; s < k; s += 4) {
-        float acc[4];
-        int jj[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int su = min(s + u, k - 1);
-            jj[u] = idx[(int64_t)n * k + su];
-            const float* w = W_encT + (int64_t)jj[u] * d;
-            float a = 0.f;
-#pragma unroll
-            for (int i = 0; i < V4; ++i) {
-                if (ok[i]) {
-                    const float4 wv = *reinterpret_cast<const float4*>(w + col[i]);
-                    a = fmaf(xr[i].x, wv.x, a); a = fmaf(xr[i].y, wv.y, a); a = fmaf(xr[i].z, wv.z, a); a = fmaf(xr[i].w, wv.w, a);
-                }
-            }
-            acc[u] = a;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[u] += __shfl_xor(acc[u], o, 64);
-        if (lane < 4 && s + lane < k) {
-            const float av = lane == 0 ? acc[0] : (lane == 1 ? acc[1] : (lane == 2 ? acc[2] : acc[3]));
-            const int jv = lane == 0 ? jj[0] : (lane == 1 ? jj[1] : (lane == 2 ? jj[2] : jj[3]));
-            const float m = val[(int64_t)n * k + s + lane];
-            const float f = (av + b_gate[jv] > 0.f && m > 0.f) ? m : 0.f;
-            val[(int64_t)n * k + s + lane] = f;
-            cnt += f > 0.f ? 1.f : 0.f;
-        }
-    }
-    cnt = wave_sum(cnt);
-    if (lane == 0) { l0part[n] = cnt; mu0[n] = 0.f; one[n] = 1.f; }
-}
-
-// threads [0, n_half): dh of the two stacked lists (dM e^r | dG is already in place), the second list's positions behind the first's;
-// threads [n_half, n_half + F): the summed counts
-__global__ __launch_bounds__(256) void gated_topk_pairs_kernel(const int32_t* __restrict__ idx, uint32_t* __restrict__ wpos,
-                                                               const uint32_t* __restrict__ cnt_m, const uint32_t* __restrict__ cnt_g,
-                                                               uint32_t* __restrict__ cnt2, const float* __restrict__ dM,
-                                                               const float* __restrict__ r_mag, float* __restrict__ dh2, int n_half, int F) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_half) {
-        const int j = i - n_half;
-        if (j < F) cnt2[j] = cnt_m[j] + cnt_g[j];
-        return;
-    }
-    dh2[i] = dM[i] * expf(r_mag[idx[i]]);                       // d mag_pre / d p = e^r (sae.py:708-712 backwards)
-    const uint32_t w = wpos[n_half + i];
-    if (w != 0xffffffffu) wpos[n_half + i] = w + cnt_m[idx[n_half + i]];
-}
-
-// per feature over its (token-ordered) list: pairs of the first list -> gb_mag = sum dM, gr_mag = sum dM (mag_pre - b_mag) (dM != 0
-// only where f = mag_pre > 0), the firing count of feature_acts; pairs of the second -> gb_gate = sum dG.  One wave per feature.
-__global__ __launch_bounds__(256) void gated_topk_feat_kernel(const uint32_t* __restrict__ offs, const int32_t* __restrict__ pairs,
-                                                              const float* __restrict__ val2, const float* __restrict__ dM,
-                                                              const float* __restrict__ dh2, const float* __restrict__ b_mag, int n_half,
-                                                              int F, float* __restrict__ gb_gate, float* __restrict__ gb_mag,
-                                                              float* __restrict__ gr_mag, float* __restrict__ fire_count,
-                                                              float* __restrict__ act_freq, float* __restrict__ n_since_fired,
-                                                              int update_stats) {
-    const int lane = threadIdx.x & 63;
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= F) return;
-    const uint32_t beg = offs[j], end = offs[j + 1];
-    float sg = 0.f, sm = 0.f, smf = 0.f, fired = 0.f;
-    for (uint32_t q = beg + lane; q < end; q += 64) {
-        const int p = pairs[q];
-        if (p < n_half) {
-            const float f = val2[p], m = dM[p];
-            sm += m;
-            smf += m * f;
-            fired += f > 0.f ? 1.f : 0.f;
-        } else {
-            sg += dh2[p];
-        }
-    }
-    sg = wave_sum(sg); sm = wave_sum(sm); smf = wave_sum(smf); fired = wave_sum(fired);
-    if (lane != 0) return;
-    gb_gate[j] = sg;
-    gb_mag[j] = sm;
-    gr_mag[j] = smf - b_mag[j] * sm;
-    if (fire_count) fire_count[j] = fired;
-    if (update_stats) {
-        act_freq[j] += fired;
-        n_since_fired[j] = fired > 0.f ? 0.f : n_since_fired[j] + 1.f;
-    }
-}
-
-__global__ __launch_bounds__(256) void gated_topk_scalars_kernel(const float* __restrict__ mse_part, const float* __restrict__ aux_part,
-                                                                 const float* __restrict__ l0part, int n_tok, float s_mse, float s_aux,
-                                                                 float s_l0, float* __restrict__ scalars) {
-    __shared__ float red[3][4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float a = 0.f, b = 0.f, e = 0.f;
-#pragma unroll 4
-    for (int i = threadIdx.x; i < n_tok; i += 256) { a += mse_part[i]; b += aux_part[i]; e += l0part[i]; }
-    a = wave_sum(a); b = wave_sum(b); e = wave_sum(e);
-    if (lane == 0) { red[0][wv] = a; red[1][wv] = b; red[2][wv] = e; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float mse = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * s_mse;
-        const float aux = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) * s_aux;
-        scalars[1] = mse; scalars[6] = aux; scalars[4] = 0.f;               // (no L1 term in the top-k form, sae.py:741-745)
-        scalars[2] = ((red[2][0] + red[2][1]) + (red[2][2] + red[2][3])) * s_l0;
-        scalars[0] = mse + aux;
-    }
-}
-}  // namespace
-
-extern "C" size_t pv_sae_gated_topk_scratch_bytes(const pv_sae_plan* plan, int32_t n_tokens) {
-    if (!plan || n_tokens < 1) return 0;
-    return gated_topk_carve(plan->d, n_tokens).total;
-}
-
-extern "C" int pv_sae_gated_topk_step(pv_sae_plan* plan, pv_sae_state* st, const float* x, int32_t N, const float* batch_mean,
-                                      int32_t n_global, int32_t flags, pv_sae_out* out, void* workspace, size_t workspace_bytes,
-                                      void* scratch, size_t scratch_bytes, void* stream_) {
-    const int update_stats = (flags & PV_SAE_UPDATE_STATS) ? 1 : 0;
-    PV_REQUIRE(plan && st && x && out && workspace && scratch && out->scalars && out->topk_idx && out->topk_val, "null argument");
-    PV_REQUIRE(sae_is_gated(st) && !sae_is_tc(st), "pv_sae_gated_topk_step needs a gated state (pv_sae_state.gt) and no transcoder");
-    const pv_sae_gated& t = st->gt;
-    PV_REQUIRE(t.r_mag && t.b_mag && t.gb_gate && t.gr_mag && t.gb_mag, "gated state");
-    PV_REQUIRE(st->W_dec && st->b_dec && st->gW_enc && st->gW_dec && st->gb_enc && st->gb_dec && st->W_encT, "state");
-    PV_REQUIRE(!update_stats || (st->act_freq_scores && st->n_fwd_since_fired), "stats buffers");
-    PV_REQUIRE(flags & PV_SAE_RENORM_DECODER, "pv_sae_gated_topk_step: PV_SAE_RENORM_DECODER is required (train_sae.py:307 is part of the step)");
-    const pv_sae_desc& d = plan->d;
-    PV_REQUIRE(N >= 1 && 2 * (int64_t)N <= d.max_tokens, "the plan must be created for 2 x the step's tokens (both k-sparse lists)");
-    PV_REQUIRE(n_global >= N, "n_global must be >= n_tokens");
-    const SaeWs ws = sae_carve(d);
-    PV_REQUIRE(workspace_bytes >= ws.total && ((uintptr_t)workspace & 255) == 0, "workspace too small / misaligned");
-    const GatedTopkWs gw = gated_topk_carve(d, N);
-    PV_REQUIRE(scratch_bytes >= gw.total && ((uintptr_t)scratch & 255) == 0, "scratch too small / misaligned (pv_sae_gated_topk_scratch_bytes)");
-    hipStream_t stream = (hipStream_t)stream_;
-    unsigned char* wsb = (unsigned char*)workspace;
-    unsigned char* gb = (unsigned char*)scratch;
-    plan->live_offs = nullptr;
-    plan->renorm_pending = false;
-    const int F = d.d_sae, D = d.d_in, k = d.k, n_half = N * k;
-    const float ng = (float)n_global;
-    int rc = pv_sae_renorm_decoder(plan, st, stream_);
-    if (rc) return rc;
-    int32_t* idx2 = out->topk_idx;
-    float* val2 = out->topk_val;
-    uint32_t* wpos2 = (uint32_t*)(wsb + ws.wpos);
-    uint32_t* cnt_g = (uint32_t*)(wsb + ws.cnt);
-    uint32_t* cnt_m = (uint32_t*)(gb + gw.cnt_m);
-    uint32_t* cnt2 = (uint32_t*)(gb + gw.cnt2);
-    float* dM = (float*)(gb + gw.dM);
-    float* dh2 = (float*)(wsb + ws.dh);
-    float* dY2 = (float*)(wsb + ws.dY);
-    float* sae_in = (float*)(wsb + ws.sae_in);
-    float* auxpart = (float*)(gb + gw.auxpart);
-    float* l0part = (float*)(gb + gw.l0part);
-    const dim3 block(256);
-    // the magnitude path's operands + its top-k (list 1)
-    const bool shadows = st->W_enc16T && st->enc_colsq;
-    hipLaunchKernelGGL(gated_scale_rows_kernel, dim3((F + 3) / 4), block, 0, stream, (const float*)st->W_encT, (const float*)t.r_mag,
-                       (float*)(gb + gw.wmagT), (_Float16*)(gb + gw.wmag16), (float*)(gb + gw.colsq), F, D);
-    PV_LAUNCH_CHECK("gated_scale_rows_kernel");
-    pv_sae_state sm = *st;
-    sm.W_encT = (float*)(gb + gw.wmagT);
-    sm.W_enc16T = shadows ? (uint16_t*)(gb + gw.wmag16) : nullptr;
-    sm.enc_colsq = shadows ? (float*)(gb + gw.colsq) : nullptr;
-    sm.b_enc = t.b_mag;
-    rc = sae_encode_topk(plan, &sm, x, N, batch_mean, idx2, val2, true, wsb, ws, stream, cnt_m, wpos2);
-    if (rc) return rc;
-#define CALL(V)                                                                                                                   \
-    hipLaunchKernelGGL((gated_topk_mask_kernel<V>), dim3((N + 3) / 4), block, 0, stream, (const float*)sae_in, (const float*)st->W_encT, \
-                       (const float*)t.b_gate, (const int32_t*)idx2, val2, l0part, (float*)(gb + gw.mu0), (float*)(gb + gw.one), N, D, k)
-    V4_DISPATCH(D, CALL);
-#undef CALL
-    PV_LAUNCH_CHECK("gated_topk_mask_kernel");
-    // the gate path's top-k (list 2)
-    pv_sae_state sg = *st;
-    sg.b_enc = t.b_gate;
-    rc = sae_encode_topk(plan, &sg, x, N, batch_mean, idx2 + n_half, val2 + n_half, true, wsb, ws, stream, cnt_g, wpos2 + n_half, true);
-    if (rc) return rc;
-    PV_HIP_CHECK(hipMemcpyAsync(sae_in + (size_t)N * D, sae_in, (size_t)N * D * 4, hipMemcpyDeviceToDevice, stream));
-    {
-        ProfScope prof(PV_PROF_SAE_BWD, stream, 8.0 * n_half * (double)D * 2.0, 0.0);
-        const dim3 grid((N + 3) / 4);
-#define CALL(V)                                                                                                                   \
-    hipLaunchKernelGGL((sae_decode_kernel<V>), grid, block, 0, stream, x, (const float*)st->W_dec, (const float*)st->b_dec,           \
-                       (const int32_t*)idx2, (const float*)val2, (const float*)(wsb + ws.mu), (const float*)(wsb + ws.sd),           \
-                       (const float*)(wsb + ws.norm), out->sae_out, dY2, dM, (float*)(wsb + ws.loss_part), N, D, k,                  \
-                       2.0f / (ng * (float)D), 1, (const float*)nullptr);                                                             \
-    hipLaunchKernelGGL((sae_decode_kernel<V>), grid, block, 0, stream, (const float*)sae_in, (const float*)st->W_dec,                  \
-                       (const float*)st->b_dec, (const int32_t*)(idx2 + n_half), (const float*)(val2 + n_half),                       \
-                       (const float*)(gb + gw.mu0), (const float*)(gb + gw.one), (const float*)(gb + gw.one), (float*)nullptr,        \
-                       dY2 + (size_t)N * D, dh2 + n_half, auxpart, N, D, k, 2.0f / ng, 1, (const float*)nullptr)
-        V4_DISPATCH(D, CALL);
-#undef CALL
-        PV_LAUNCH_CHECK("sae_decode_kernel (top-k gated)");
-        hipLaunchKernelGGL(gated_topk_pairs_kernel, dim3((n_half + F + 255) / 256), block, 0, stream, (const int32_t*)idx2, wpos2,
-                           (const uint32_t*)cnt_m, (const uint32_t*)cnt_g, cnt2, (const float*)dM, (const float*)t.r_mag, dh2, n_half, F);
-        PV_LAUNCH_CHECK("gated_topk_pairs_kernel");
-        SaeBwd b;                                                   // (statistics and fire_count: gated_topk_feat_kernel)
-        b.N = 2 * N; b.k = k; b.idx = idx2; b.val = val2; b.dY = dY2; b.sae_in = sae_in; b.scalars = out->scalars;
-        b.tail = sae_tail(wsb, ws, (size_t)2 * n_half);             // (tail.dh = dh2, tail.wpos = wpos2)
-        b.cnt = cnt2;
-        rc = sae_csr_backward(plan, st, b, wsb, ws, stream);
-        if (rc) return rc;
-        hipLaunchKernelGGL(gated_topk_feat_kernel, dim3((F + 3) / 4), block, 0, stream, (const uint32_t*)(wsb + ws.offs),
-                           (const int32_t*)b.tail.pairs, (const float*)val2, (const float*)dM, (const float*)dh2, (const float*)t.b_mag, n_half,
-                           F, t.gb_gate, t.gb_mag, t.gr_mag, out->fire_count, st->act_freq_scores, st->n_fwd_since_fired, update_stats);
-        hipLaunchKernelGGL(gated_topk_scalars_kernel, dim3(1), block, 0, stream, (const float*)(wsb + ws.loss_part), (const float*)auxpart,
-                           (const float*)l0part, N, 1.0f / (ng * (float)D), 1.0f / ng, 1.0f / (float)N, out->scalars);
-        PV_LAUNCH_CHECK("top-k gated kernels");
-        // gb_dec = colsum(dY) + 2 colsum(dVia) - W_enc colsum(dP) (as pv_sae_gated_step); b_enc takes no part
-        rc = sae_gated_gbdec(d, st, dY2, N, (float*)(gb + gw.tmpd), (float*)(gb + gw.cspart), wsb, ws, stream);
-        if (rc) return rc;
     }
     return PV_OK;
 }
@@ -1801,8 +1070,8 @@ extern "C" int pv_sae_step(pv_sae_plan* plan, pv_sae_state* st, const float* x, 
     const float* inv_norm = nullptr;
     plan->renorm_pending = renorm;
     if (renorm && !(flags & PV_SAE_INV_NORM_VALID)) {
-        hipLaunchKernelGGL(dec_inv_norm_kernel, dim3((d.d_sae + 15) / 16), dim3(256), 0, stream, (const float*)st->W_dec,
-                           st->dec_inv_norm, d.d_sae, d.d_in);
+        const int rn = sae_dec_inv_norm(d, st, stream);
+        if (rn) return rn;
     }
     if (renorm) inv_norm = st->dec_inv_norm;
     PV_REQUIRE(!sae_is_gated(st), "pv_sae_step does not serve a gated state: pv_sae_gated_step");
@@ -1836,351 +1105,5 @@ extern "C" int pv_sae_step(pv_sae_plan* plan, pv_sae_state* st, const float* x, 
                            (const float*)(wsb + ws.rowsq), d.d_sae, out->scalars);
         PV_LAUNCH_CHECK("sqnorm_blocks_kernel");
     }
-    return PV_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Feature-parallel step: this rank's engine covers a SHARD of the features; the top-k is taken over all ranks'
-// candidates by the caller, the local candidates that did not make it arrive here with value 0 -- and a pair with
-// value <= 0 is a hole everywhere (no decode contribution, no CSR entry, dh gated off), like the reference's ReLU behind
-// its top-k.  pv_sae_step cut at the reconstruction:
-//   pv_sae_encode_topk (this rank's k candidates per token)  ->  [all-gather of candidate values, global top-k: caller]
-//   pv_sae_tp_partial  (partial reconstruction of the kept pairs)  ->  [all-reduce of the partials: caller]
-//   pv_sae_tp_finish   (LN-out, loss, dY, dh, CSR, sparse backward, statistics for the shard's features)
-//   -> [gb_dec / clip norm / l0 all-reduces: caller] -> pv_sae_apply
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sae_recount_kernel(const int32_t* __restrict__ idx, const float* __restrict__ val,
-                                                          uint32_t* __restrict__ cnt, uint32_t* __restrict__ wpos, int n_pairs) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_pairs) return;
-    wpos[i] = val[i] > 0.f ? atomicAdd(&cnt[idx[i]], 1u) : 0xffffffffu;
-}
-
-extern "C" int pv_sae_tp_partial(pv_sae_plan* plan, pv_sae_state* st, const int32_t* topk_idx, const float* topk_val, int32_t N,
-                                 int32_t flags, float* partial, void* stream_) {
-    PV_REQUIRE(!st || !sae_is_gated(st), "this entry point does not serve a gated state (pv_sae_state.gt)");
-    PV_REQUIRE(!st || !sae_is_tc(st), "pv_sae_tp_partial: not available for a transcoder state (pv_sae_state.tc)");
-    PV_REQUIRE(plan && st && topk_idx && topk_val && partial && st->W_dec, "null argument");
-    const pv_sae_desc& d = plan->d;
-    PV_REQUIRE(N >= 1 && N <= d.max_tokens, "n_tokens exceeds plan max_tokens");
-    hipStream_t stream = (hipStream_t)stream_;
-    const bool renorm = (flags & PV_SAE_RENORM_DECODER) != 0;
-    PV_REQUIRE(!renorm || st->dec_inv_norm, "PV_SAE_RENORM_DECODER needs pv_sae_state.dec_inv_norm");
-    plan->renorm_pending = renorm;
-    plan->live_offs = nullptr;
-    if (renorm && !(flags & PV_SAE_INV_NORM_VALID))
-        hipLaunchKernelGGL(dec_inv_norm_kernel, dim3((d.d_sae + 15) / 16), dim3(256), 0, stream, (const float*)st->W_dec,
-                           st->dec_inv_norm, d.d_sae, d.d_in);
-    const float* inv_norm = renorm ? (const float*)st->dec_inv_norm : nullptr;
-    const dim3 grid((N + 3) / 4), block(256);
-#define CALL(D)                                                                                                          \
-    hipLaunchKernelGGL((sae_decode_kernel<D, 1>), grid, block, 0, stream, (const float*)nullptr, (const float*)st->W_dec, \
-                       (const float*)nullptr, topk_idx, topk_val, (const float*)nullptr, (const float*)nullptr,          \
-                       (const float*)nullptr, partial, (float*)nullptr, (float*)nullptr, (float*)nullptr, N, d.d_in, d.k, \
-                       0.f, 0, inv_norm, (const float*)nullptr)
-    V4_DISPATCH(d.d_in, CALL);
-#undef CALL
-    PV_LAUNCH_CHECK("sae_decode_kernel (partial)");
-    return PV_OK;
-}
-
-// `workspace` must be the one the preceding pv_sae_encode_topk ran in, on the same x (it holds the LN statistics, the
-// loss normaliser and sae_in); pre_sum [N, d_in] = the reconstruction summed over the ranks (without b_dec).  Gradients of
-// the shard's rows are WRITTEN into st->g*; st->gb_dec receives colsum(dY) - W_enc[:, shard] gb_enc[shard]: the caller
-// combines the ranks' encoder terms.  scalars[0..1] = loss (over the full batch, replicated), scalars[2] = this rank's
-// kept pairs per token (the ranks' values add up to l0).
-extern "C" int pv_sae_tp_finish(pv_sae_plan* plan, pv_sae_state* st, const float* x, const float* pre_sum, const int32_t* topk_idx,
-                                const float* topk_val, int32_t N, int32_t n_global, int32_t flags, pv_sae_out* out,
-                                void* workspace, size_t workspace_bytes, void* stream_) {
-    PV_REQUIRE(!st || !sae_is_gated(st), "this entry point does not serve a gated state (pv_sae_state.gt)");
-    PV_REQUIRE(!st || !sae_is_tc(st), "pv_sae_tp_finish: not available for a transcoder state (pv_sae_state.tc)");
-    const int update_stats = (flags & PV_SAE_UPDATE_STATS) ? 1 : 0;
-    PV_REQUIRE(plan && st && x && pre_sum && topk_idx && topk_val && out && workspace, "null argument");
-    PV_REQUIRE(out->scalars, "pv_sae_out.scalars");
-    PV_REQUIRE(st->W_dec && st->b_enc && st->b_dec && st->gW_enc && st->gW_dec && st->gb_enc && st->gb_dec, "state");
-    PV_REQUIRE(st->W_encT, "the transposed encoder copy (pv_sae_state.W_encT) is required");
-    PV_REQUIRE(!update_stats || (st->act_freq_scores && st->n_fwd_since_fired), "stats buffers");
-    const pv_sae_desc& d = plan->d;
-    PV_REQUIRE(N >= 1 && N <= d.max_tokens, "n_tokens exceeds plan max_tokens");
-    PV_REQUIRE(n_global >= N, "n_global must be >= n_tokens");
-    const SaeWs ws = sae_carve(d);
-    PV_REQUIRE(workspace_bytes >= ws.total, "workspace too small");
-    hipStream_t stream = (hipStream_t)stream_;
-    unsigned char* wsb = (unsigned char*)workspace;
-    const int k = d.k, n_pairs = N * k;
-    const float* inv_norm = plan->renorm_pending ? (const float*)st->dec_inv_norm : nullptr;       // as pv_sae_tp_partial left it
-    plan->live_offs = nullptr;
-    float* dY = (float*)(wsb + ws.dY);
-    float* dh = (float*)(wsb + ws.dh);
-    float* sae_in = (float*)(wsb + ws.sae_in);
-    uint32_t* cnt = (uint32_t*)(wsb + ws.cnt);
-    uint32_t* wposp = (uint32_t*)(wsb + ws.wpos);
-    const dim3 block(256);
-    // the pairs that survived the global top-k: counts and within-list positions afresh
-    PV_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)d.d_sae * 4, stream));
-    hipLaunchKernelGGL(sae_recount_kernel, dim3((n_pairs + 255) / 256), block, 0, stream, topk_idx, topk_val, cnt, wposp, n_pairs);
-    // sae_fold means here what it means for pv_sae_step (sae_sparse_tail): folded, the CSR scan is one more workgroup
-    // of the decode launch, the loss rides in the post + fill launch and both list sorts are one launch -- 11 launches instead of 13
-    const bool folded = g_pv_tuning.sae_fold != 0;
-    const float grad_scale = 2.0f / ((float)n_global * (float)d.d_in);
-    ScanRole scan = {};
-    if (folded) {
-        scan.cnt = (const uint32_t*)cnt; scan.offs = (uint32_t*)(wsb + ws.offs); scan.n_long = (uint32_t*)(wsb + ws.n_long);
-        scan.d_sae = d.d_sae; scan.scalars = out->scalars; scan.tokens = (float)N;
-    }
-    const dim3 grid((N + 3) / 4 + (folded ? 1 : 0));
-#define CALL(D)                                                                                                        \
-    hipLaunchKernelGGL((sae_decode_kernel<D, 2>), grid, block, 0, stream, x, (const float*)st->W_dec, (const float*)st->b_dec, \
-                       topk_idx, topk_val, (const float*)(wsb + ws.mu), (const float*)(wsb + ws.sd),                    \
-                       (const float*)(wsb + ws.norm), out->sae_out, dY, dh, (float*)(wsb + ws.loss_part), N, d.d_in, k, \
-                       grad_scale, 1, inv_norm, pre_sum, (const float*)nullptr, 0.f, (const uint32_t*)nullptr,          \
-                       (const uint32_t*)nullptr, scan)
-    V4_DISPATCH(d.d_in, CALL);
-#undef CALL
-    PV_LAUNCH_CHECK("sae_decode_kernel (finish)");
-    SaeBwd b;
-    b.N = N; b.k = k; b.idx = topk_idx; b.val = topk_val; b.dY = dY; b.sae_in = sae_in; b.scalars = out->scalars;
-    b.tail = sae_tail(wsb, ws, (size_t)n_pairs);
-    b.fire_count = out->fire_count; b.update_stats = update_stats;
-    b.loss_part = (const float*)(wsb + ws.loss_part); b.loss_scale = 1.0f / ((float)n_global * (float)d.d_in);
-    b.colsum_dY = true; b.folded = folded;
-    const int rc = sae_csr_backward(plan, st, b, wsb, ws, stream);
-    if (rc) return rc;
-    const int nblk = (N + CS_ROWS - 1) / CS_ROWS, ngb = (d.d_sae + GBD_ROWS - 1) / GBD_ROWS;
-    float* colpart = (float*)(wsb + ws.colpart);
-    hipLaunchKernelGGL(sae_gbdec_partial_kernel, dim3(ngb), dim3(256), 0, stream, (const float*)st->W_encT, (const float*)st->gb_enc,
-                       colpart + (size_t)nblk * d.d_in, d.d_sae, d.d_in);
-    // PV_SAE_TP_ENC_TERM_ONLY: every rank holds the same dY; only one of them contributes its column sum to the all-reduce
-    if (flags & PV_SAE_TP_ENC_TERM_ONLY)
-        hipLaunchKernelGGL(colsum_final_kernel, dim3((d.d_in + 63) / 64), dim3(1024), 0, stream,
-                           (const float*)(colpart + (size_t)nblk * d.d_in), st->gb_dec, ngb, d.d_in, 1.0f);
-    else
-        hipLaunchKernelGGL(colsum_final_kernel, dim3((d.d_in + 63) / 64), dim3(1024), 0, stream, (const float*)colpart, st->gb_dec,
-                           nblk + ngb, d.d_in, 1.0f);
-    PV_LAUNCH_CHECK("sae bias-grad kernels");
-    return PV_OK;
-}
-
-// ---- feature-parallel glue kernels: the global top-k over the ranks' candidates, and the ONE small all-reduce bucket ----
-// gathered [W][2][N][k]: rank r's piece = its k candidate values per token (float bits, sorted or not) followed by their
-// LOCAL feature indices (global index = r * shard + local).  A wave per token: lane s owns this rank's candidate s and
-// counts the candidates of all ranks that come before it in the order (value desc, global feature index asc) -- torch.topk's
-// order on the dense row, as the oracle -- out of an LDS copy of the token's W k candidates; rank < k = kept, otherwise
-// the value becomes 0 (a hole).  Replaces two argsorts over [N, W k] and a scatter on the host side.
-__global__ __launch_bounds__(256) void sae_tp_merge_kernel(const int32_t* __restrict__ gathered, int W, int rank, int n_tok, int k,
-                                                           int shard, float* __restrict__ val_kept) {
-    __shared__ float sv[4][8 * MAXK];
-    __shared__ int32_t sg[4][8 * MAXK];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int n = blockIdx.x * 4 + wv;
-    if (n >= n_tok) return;                                    // (whole waves leave; no workgroup barrier below)
-    const int64_t piece = 2 * (int64_t)n_tok * k;
-    const int total = W * k;
-    for (int c = lane; c < total; c += 64) {
-        const int r = c / k, t = c - r * k;
-        const int32_t* pr = gathered + r * piece + (int64_t)n * k + t;
-        sv[wv][c] = __int_as_float(pr[0]);
-        sg[wv][c] = r * shard + pr[(int64_t)n_tok * k];
-    }
-    __builtin_amdgcn_wave_barrier();                            // (a wave's LDS operations execute in order)
-    if (lane < k) {
-        const float v = sv[wv][rank * k + lane];
-        const int32_t g = sg[wv][rank * k + lane];
-        int before = 0;
-        for (int c = 0; c < total; ++c) {
-            const float vo = sv[wv][c];
-            before += (vo > v) || (vo == v && sg[wv][c] < g);
-        }
-        val_kept[(int64_t)n * k + lane] = before < k ? v : 0.f;
-    }
-}
-
-extern "C" int pv_sae_tp_merge(const int32_t* gathered, int32_t world, int32_t rank, int32_t N, int32_t k, int32_t shard,
-                               float* val_kept, void* stream_) {
-    PV_REQUIRE(gathered && val_kept, "null argument");
-    PV_REQUIRE(world >= 1 && world <= 8 && rank >= 0 && rank < world, "world size must be in [1, 8]");
-    PV_REQUIRE(k >= 1 && k <= MAXK && N >= 1 && shard >= k, "shape");
-    hipLaunchKernelGGL(sae_tp_merge_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream_, gathered, world, rank, N, k, shard,
-                       val_kept);
-    PV_LAUNCH_CHECK("sae_tp_merge_kernel");
-    return PV_OK;
-}
-
-// The bucket every rank all-reduces once per step: [gb_dec (d_in) | rows term of the clip norm | kept pairs per token | 2 pad |
-// firing counts of ALL features (d_sae_total)].  pv_sae_tp_finish has already written this rank's gb_dec term and its
-// shard's firing counts in place (the caller points st->gb_dec / out->fire_count into the bucket); pack adds the two
-// scalars and zeroes the other ranks' firing counts.  After the all-reduce, unpack forms the clip norm of the GLOBAL
-// gradient: the ranks' row terms + ||gb_dec||^2 of the summed gb_dec.
-__global__ __launch_bounds__(1024) void sae_tp_bucket_pack_kernel(const float* __restrict__ rowsq, int d_shard, const float* __restrict__ scalars,
-                                                                  float* __restrict__ bucket, int d_in, int j_lo, int d_total) {
-    __shared__ float red[16];
-    float s = 0.f;
-    for (int j = threadIdx.x; j < d_shard; j += 1024) s += rowsq[j];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    float* fire = bucket + d_in + 4;
-    for (int j = threadIdx.x; j < d_total; j += 1024)
-        if (j < j_lo || j >= j_lo + d_shard) fire[j] = 0.f;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < 16; ++w) t += red[w];
-        bucket[d_in] = t;
-        bucket[d_in + 1] = scalars[2];
-        bucket[d_in + 2] = 0.f;
-        bucket[d_in + 3] = 0.f;
-    }
-}
-__global__ __launch_bounds__(1024) void sae_tp_bucket_unpack_kernel(const float* __restrict__ bucket, int d_in, float* __restrict__ scalars) {
-    __shared__ float red[16];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < d_in; i += 1024) s += bucket[i] * bucket[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < 16; ++w) t += red[w];
-        scalars[3] = bucket[d_in] + t;
-        scalars[2] = bucket[d_in + 1];
-    }
-}
-
-extern "C" int pv_sae_tp_bucket_pack(pv_sae_plan* plan, const void* workspace, const float* scalars, float* bucket, int32_t j_lo,
-                                     int32_t d_sae_total, void* stream_) {
-    PV_REQUIRE(plan && workspace && scalars && bucket, "null argument");
-    const pv_sae_desc& d = plan->d;
-    PV_REQUIRE(j_lo >= 0 && j_lo + d.d_sae <= d_sae_total, "shard range");
-    const SaeWs ws = sae_carve(d);
-    hipLaunchKernelGGL(sae_tp_bucket_pack_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream_,
-                       (const float*)((const unsigned char*)workspace + ws.rowsq), d.d_sae, scalars, bucket, d.d_in, j_lo, d_sae_total);
-    PV_LAUNCH_CHECK("sae_tp_bucket_pack_kernel");
-    return PV_OK;
-}
-extern "C" int pv_sae_tp_bucket_unpack(pv_sae_plan* plan, const float* bucket, float* scalars, void* stream_) {
-    PV_REQUIRE(plan && bucket && scalars, "null argument");
-    hipLaunchKernelGGL(sae_tp_bucket_unpack_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream_, bucket, plan->d.d_in, scalars);
-    PV_LAUNCH_CHECK("sae_tp_bucket_unpack_kernel");
-    return PV_OK;
-}
-
-// the same number from the per-feature terms the last pv_sae_step left in its workspace
-extern "C" int pv_sae_grad_sqnorm_step(pv_sae_plan* plan, const pv_sae_state* st, const void* workspace, float* scalars, void* stream_) {
-    PV_REQUIRE(plan && st && workspace && scalars && st->gb_dec, "null argument");
-    const pv_sae_desc& d = plan->d;
-    const SaeWs ws = sae_carve(d);
-    const bool tc = sae_is_tc(st);
-    PV_REQUIRE(!tc || st->tc.gb_dec_out, "transcoder state");
-    hipLaunchKernelGGL(sqnorm_rowsq_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream_,
-                       (const float*)((const unsigned char*)workspace + ws.rowsq), d.d_sae, (const float*)st->gb_dec, d.d_in, scalars,
-                       tc ? (const float*)st->tc.gb_dec_out : (const float*)nullptr, tc ? d.d_in : 0,
-                       (tc && st->tc.gW_skip) ? (const float*)st->tc.gW_skip : (const float*)nullptr,
-                       (tc && st->tc.gW_skip) ? d.d_in * d.d_in : 0);
-    PV_LAUNCH_CHECK("sqnorm_rowsq_kernel");
-    return PV_OK;
-}
-
-// sum of squares of a flat gradient buffer -> scalars[3]; `partial` = 1024 floats of scratch
-extern "C" int pv_sae_grad_sqnorm(const float* flat_grads, int64_t n, float* partial, float* scalars, void* stream_) {
-    PV_REQUIRE(flat_grads && partial && scalars && n > 0, "null argument");
-    PV_REQUIRE(pv_aligned16(flat_grads), "gradient buffer must be 16-byte aligned");
-    hipStream_t stream = (hipStream_t)stream_;
-    hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(1024), dim3(256), 0, stream, flat_grads, n, partial);
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, stream, (const float*)partial, scalars, 1024, 1.0f, 3, -1);
-    PV_LAUNCH_CHECK("sqnorm kernels");
-    return PV_OK;
-}
-
-// The same over the gradient rows of features [j_lo, j_hi) only (gW_enc^T, gW_dec, gb_enc slices; + gb_dec when
-// include_b_dec): the local term of the sharded optimizer's clip norm (the ranks' terms are summed by one scalar all-reduce).
-extern "C" int pv_sae_grad_sqnorm_rows(pv_sae_plan* plan, const pv_sae_state* st, int32_t j_lo, int32_t j_hi, int32_t include_b_dec,
-                                       float* partial, float* scalars, void* stream_) {
-    PV_REQUIRE(plan && st && partial && scalars && st->gW_enc && st->gW_dec && st->gb_enc && st->gb_dec, "null argument");
-    const pv_sae_desc& d = plan->d;
-    PV_REQUIRE(j_lo >= 0 && j_lo <= j_hi && j_hi <= d.d_sae, "feature range");
-    hipStream_t stream = (hipStream_t)stream_;
-    PV_HIP_CHECK(hipMemsetAsync(partial, 0, 1024 * 4, stream));
-    const int64_t nrow = (int64_t)(j_hi - j_lo) * d.d_in;
-    if (nrow > 0) {
-        PV_REQUIRE(((int64_t)j_lo * d.d_in) % 4 == 0, "slice must start on a 16-byte boundary");
-        hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(384), dim3(256), 0, stream, (const float*)st->gW_enc + (int64_t)j_lo * d.d_in, nrow, partial);
-        hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(384), dim3(256), 0, stream, (const float*)st->gW_dec + (int64_t)j_lo * d.d_in, nrow, partial + 384);
-        hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(8), dim3(256), 0, stream, (const float*)st->gb_enc + j_lo, (int64_t)(j_hi - j_lo), partial + 768);
-    }
-    if (include_b_dec)
-        hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(8), dim3(256), 0, stream, (const float*)st->gb_dec, (int64_t)d.d_in, partial + 776);
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, stream, (const float*)partial, scalars, 1024, 1.0f, 3, -1);
-    PV_LAUNCH_CHECK("sqnorm kernels");
-    return PV_OK;
-}
-
-extern "C" int pv_sae_apply(pv_sae_plan* plan, pv_sae_state* st, const float* scalars, float max_grad_norm, float lr,
-                            int32_t step, int32_t j_lo, int32_t j_hi, void* stream_) {
-    PV_REQUIRE(plan && st && scalars && step >= 1, "null argument / step must be >= 1");
-    PV_REQUIRE(st->mW_enc && st->mW_dec && st->mb_enc && st->mb_dec && st->vW_enc && st->vW_dec && st->vb_enc && st->vb_dec, "Adam state");
-    PV_REQUIRE(st->W_encT && st->W_enc16T && st->enc_colsq, "encoder shadows");
-    hipStream_t stream = (hipStream_t)stream_;
-    const pv_sae_desc& d = plan->d;
-    PV_REQUIRE(j_lo >= 0 && j_lo <= j_hi && j_hi <= d.d_sae, "feature range");
-    // (every check stands in front of the first launch: a call that returns an error has not touched the state)
-    if (sae_is_tc(st)) {
-        const pv_sae_transcoder& t = st->tc;
-        PV_REQUIRE(t.gb_dec_out && t.mb_dec_out && t.vb_dec_out && (!t.W_skip || (t.gW_skip && t.mW_skip && t.vW_skip)), "transcoder Adam state");
-    }
-    if (sae_is_gated(st)) {
-        const pv_sae_gated& t = st->gt;
-        PV_REQUIRE(t.r_mag && t.b_mag && t.gb_gate && t.gr_mag && t.gb_mag && t.mb_gate && t.mr_mag && t.mb_mag && t.vb_gate && t.vr_mag && t.vb_mag,
-                   "gated Adam state");
-        PV_REQUIRE(j_lo == 0 && j_hi == d.d_sae, "gated SAE: the whole feature range");
-    }
-    AdamC c;
-    c.lr = lr; c.b1 = 0.9f; c.b2 = 0.999f; c.eps = 1e-8f; c.max_norm = max_grad_norm;
-    c.bc1 = (float)(1.0 - pow(0.9, (double)step));
-    c.bc2_sqrt = (float)sqrt(1.0 - pow(0.999, (double)step));
-    const int nj = j_hi - j_lo;
-    // algorithmic bytes: 7 x 4 per parameter (w, g, m, v read; w, m, v written) + the two extra copies of W_enc (fp32 + fp16)
-    ProfScope prof(PV_PROF_SAE_APPLY, stream, 0.0, 7.0 * 4.0 * (2.0 * d.d_in * (double)nj + nj + d.d_in) + 6.0 * d.d_in * (double)nj);
-    const dim3 block(256);
-    AdamVec2 v2;
-    v2.W0 = st->b_enc; v2.G0 = (const float*)st->gb_enc; v2.M0 = st->mb_enc; v2.V0 = st->vb_enc; v2.lo0 = j_lo; v2.hi0 = j_hi;
-    v2.nb0 = (nj + 255) / 256; v2.W1 = st->b_dec; v2.G1 = (const float*)st->gb_dec; v2.M1 = st->mb_dec; v2.V1 = st->vb_dec; v2.hi1 = d.d_in;
-    bool vec2_done = false;
-    if (nj > 0) {
-        const float* inv_norm = plan->renorm_pending ? (const float*)st->dec_inv_norm : nullptr;
-#define CALL(D) hipLaunchKernelGGL((adam_wdec_kernel<D>), dim3((nj + 3) / 4), block, 0, stream, st->W_dec, (const float*)st->gW_dec, st->mW_dec, st->vW_dec, scalars, c, j_lo, j_hi, d.d_in, inv_norm, st->dec_inv_norm, plan->live_offs)
-        V4_DISPATCH(d.d_in, CALL);
-#undef CALL
-        if (st->W_enc) {
-            hipLaunchKernelGGL((wenc_rows_kernel<0>), dim3((nj + 31) / 32), block, 0, stream, st->W_enc, st->W_encT, (_Float16*)st->W_enc16T,
-                               st->enc_colsq, (const float*)st->gW_enc, st->mW_enc, st->vW_enc, scalars, c, d.d_in, d.d_sae, j_lo, j_hi,
-                               plan->live_offs);
-        } else {                                                  // lazy parameter layout: everything stays in the transposed domain
-            // (the two bias vectors ride at the end of this launch)
-            vec2_done = g_pv_tuning.sae_fold != 0;
-            const int nb_rows = (nj + 3) / 4, nb_v2 = vec2_done ? v2.nb0 + (d.d_in + 255) / 256 : 0;
-#define CALL(D) hipLaunchKernelGGL((adam_wenct_kernel<D>), dim3(nb_rows + nb_v2), block, 0, stream, st->W_encT, (_Float16*)st->W_enc16T, st->enc_colsq, (const float*)st->gW_enc, st->mW_enc, st->vW_enc, scalars, c, j_lo, j_hi, d.d_in, plan->live_offs, nb_rows, v2)
-            V4_DISPATCH(d.d_in, CALL);
-#undef CALL
-        }
-    }
-    if (!vec2_done)     // b_enc's feature range and b_dec: one launch
-        hipLaunchKernelGGL(adam_vec2_kernel, dim3(v2.nb0 + (d.d_in + 255) / 256), block, 0, stream, v2, scalars, c);
-    if (sae_is_tc(st)) {                                               // transcoder: plain Adam on the decoder's own bias and the skip matrix
-        const pv_sae_transcoder& t = st->tc;
-        hipLaunchKernelGGL(adam_vec_kernel, dim3((d.d_in + 255) / 256), block, 0, stream, t.b_dec_out, (const float*)t.gb_dec_out,
-                           t.mb_dec_out, t.vb_dec_out, scalars, c, 0, d.d_in);
-        if (t.W_skip)
-            hipLaunchKernelGGL(adam_vec_kernel, dim3((d.d_in * d.d_in + 255) / 256), block, 0, stream, t.W_skip, (const float*)t.gW_skip,
-                               t.mW_skip, t.vW_skip, scalars, c, 0, d.d_in * d.d_in);
-    }
-    if (sae_is_gated(st)) {                                            // gated SAE: plain Adam on b_gate, r_mag, b_mag
-        const pv_sae_gated& t = st->gt;
-        const dim3 gv((d.d_sae + 255) / 256);
-        hipLaunchKernelGGL(adam_vec_kernel, gv, block, 0, stream, t.b_gate, (const float*)t.gb_gate, t.mb_gate, t.vb_gate, scalars, c, 0, d.d_sae);
-        hipLaunchKernelGGL(adam_vec_kernel, gv, block, 0, stream, t.r_mag, (const float*)t.gr_mag, t.mr_mag, t.vr_mag, scalars, c, 0, d.d_sae);
-        hipLaunchKernelGGL(adam_vec_kernel, gv, block, 0, stream, t.b_mag, (const float*)t.gb_mag, t.mb_mag, t.vb_mag, scalars, c, 0, d.d_sae);
-    }
-    PV_LAUNCH_CHECK("adam kernels");
-    if (j_lo == 0 && j_hi == d.d_sae) plan->renorm_pending = false;      // (a sharded apply leaves the other ranks' rows to the all-gather)
     return PV_OK;
 }

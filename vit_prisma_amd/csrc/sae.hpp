@@ -1,5 +1,7 @@
-// Shared definitions of the SAE step (sae.hip: prep / decode / Adam; sae_bwd.hip: the sparse backward; sae_enc.hip: the encoder + top-k;
-// sae_dense.hip, sae_dense_gemm.hip, sae_ghost.hip, sae_gated.hip: the dense ReLU + L1 step, its GEMM, ghost gradients, the gated step).
+// Shared definitions of the SAE step (sae.hip: prep / exact top-k / decode / bias gradients, the plan, the k-sparse step; sae_bwd.hip: the
+// sparse backward; sae_enc.hip: the filtered encoder + top-k; sae_apply.hip: clip norm, Adam, renorm, encoder shadows; sae_tp.hip: the
+// feature-parallel step; sae_dense.hip, sae_dense_gemm.hip, sae_ghost.hip: the dense ReLU + L1 step, its GEMM, ghost gradients;
+// sae_gated.hip, sae_gated_topk.hip: the gated step on the dense GEMM / in its top-k form).
 #pragma once
 #include "gemm.hpp"
 #include "prof.hpp"
@@ -243,6 +245,12 @@ int sae_encode_fast(const pv_sae_desc& d, const pv_sae_state* st, int N, int32_t
 // else the rows row_list[0 .. *n_list) are walked by `slots` workgroups.
 void sae_topk_rows(const float* hidden, int32_t* idx_out, float* val_out, int d_sae, int k, int n_rows, const int32_t* row_list,
                    const uint32_t* n_list, int slots, uint32_t* feat_cnt, uint32_t* wpos, hipStream_t stream);
+// sae.hip: prep + the encoder (filtered where pv_sae_fast_ok and the shadows allow, else exact) + top-k of N tokens.  want_csr: also
+// count the kept pairs per feature (ws.cnt) and record their positions (ws.wpos) for the backward; cnt_over / wpos_over: other
+// destinations for those two (the top-k gated step encodes twice); skip_prep: sae_prep has already run on x
+int sae_encode_topk(pv_sae_plan* plan, const pv_sae_state* st, const float* x, int N, const float* batch_mean,
+                    int32_t* topk_idx, float* topk_val, bool want_csr, unsigned char* wsb, const SaeWs& ws, hipStream_t stream,
+                    uint32_t* cnt_over = nullptr, uint32_t* wpos_over = nullptr, bool skip_prep = false);
 
 // ---- the sparse form of the ReLU + L1 step (pv_sae_relu_step, sae_dense.hip) -------------------------------------------------
 constexpr int PV_SAE_RELU_SLOTS = 32;        // candidate slots per (token, 256-feature tile) of the ReLU filter
@@ -284,9 +292,16 @@ int sae_dec_inv_norm(const pv_sae_desc& d, const pv_sae_state* st, hipStream_t s
 int sae_prep(const pv_sae_desc& d, const float* x, const float* b_dec, const float* batch_mean, int N, bool want_filter_inputs,
              unsigned char* wsb, const SaeWs& ws, hipStream_t stream, int d_true = 0, SaePre* pre = nullptr,
              const pv_sae_state* st = nullptr, uint32_t* feat_cnt = nullptr);
-// sq_scalars: also leave sq_scalars[3] = the gradient's sum of squares (PV_SAE_FUSED_SQNORM)
+// the bias gradients: st->gb_dec = -W_enc gb_enc (the encoder-input path of b_dec) and colsum(dY), which goes ...
+enum SaeDyTo {
+    SAE_DY_TO_GB_DEC,        // ... into gb_dec with the encoder term (an autoencoder's b_dec plays both roles)
+    SAE_DY_TO_GB_DEC_OUT,    // ... to tc.gb_dec_out, in a launch of its own (a transcoder: the two roles are two parameters)
+    SAE_DY_NOWHERE,          // ... nowhere (PV_SAE_TP_ENC_TERM_ONLY: another rank contributes it to the all-reduce)
+};
+// have_colsum: the 16-row partial column sums of dY are in ws.colpart already (SaeBwd.colsum_dY)
+// sq_scalars (with SAE_DY_TO_GB_DEC): also leave sq_scalars[3] = the gradient's sum of squares (PV_SAE_FUSED_SQNORM)
 int sae_gbdec(const pv_sae_desc& d, const pv_sae_state* st, const float* dY, int N, unsigned char* wsb, const SaeWs& ws,
-              hipStream_t stream, bool have_colsum = false, float* sq_scalars = nullptr);
+              hipStream_t stream, SaeDyTo dy_to, bool have_colsum = false, float* sq_scalars = nullptr);
 void sae_reduce_sum(const float* v, float* out, int n, float scale, int slot, int slot2, hipStream_t stream,
                     const uint32_t* gate = nullptr, uint32_t want = 0u);
 int sae_colsum(const float* x, int rows, int d, float* out, float scale, float* partial, hipStream_t stream);
@@ -305,9 +320,7 @@ int sae_tc_require(const pv_sae_desc& d, const pv_sae_state* st, int N);        
 // sae.hip: the loss normaliser of the TARGET (sae.py:145-147 on y) -> ws.norm; batch_mean = mean_n(target) or NULL (computed here)
 int sae_tc_target_norm(const pv_sae_desc& d, const pv_sae_state* st, const float* batch_mean, int N, unsigned char* wsb, const SaeWs& ws,
                        hipStream_t stream);
-// sae.hip: gb_dec_out = colsum(dY), gb_dec = -W_enc gb_enc (the two roles of the autoencoder's b_dec are two parameters here)
-int sae_tc_bias_grads(const pv_sae_desc& d, const pv_sae_state* st, const float* dY, int N, unsigned char* wsb, const SaeWs& ws,
-                      hipStream_t stream);
+// (its bias gradients: sae_gbdec with SAE_DY_TO_GB_DEC_OUT)
 // sae_dense.hip: skip term [N, d_in] = x @ W_skip^T at the head of tc.scratch (returns nullptr through *skip when there is no
 // W_skip); gW_skip = dY^T x
 int sae_tc_skip_forward(const pv_sae_desc& d, const pv_sae_state* st, const float* x, int N, const float** skip, hipStream_t stream);

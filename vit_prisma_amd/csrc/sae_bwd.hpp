@@ -1,6 +1,7 @@
 // The sparse backward of the k-sparse SAE steps (sae_bwd.hip): the CSR by feature of the kept (token, slot) pairs and the gradient
-// kernels behind it.  Here: what its callers fill in (SaeBwd), the sizes the workspace carvers need, and the device bodies that kernels
-// of sae.hip, sae_bwd.hip and sae_gated.hip share.
+// kernels behind it, and the decode launch in front of it (sae_decode, sae.hip).  Here: what their callers (sae.hip, sae_tp.hip,
+// sae_gated_topk.hip, sae_dense.hip, sae_gated.hip) fill in (SaeDecode, SaeBwd), the sizes the workspace carvers need, and the device
+// bodies that kernels of sae.hip, sae_bwd.hip, sae_apply.hip, sae_gated.hip and sae_gated_topk.hip share.
 #pragma once
 #include "sae.hpp"
 
@@ -179,5 +180,43 @@ __device__ __forceinline__ void loss_reduce_body(const float* __restrict__ loss_
     }
 }
 
+// the scan as a role of a decode launch over the pair counts cnt of N tokens: offsets -> ws.offs, scalars[2] = l0
+static inline ScanRole sae_scan_role(const pv_sae_desc& d, unsigned char* wsb, const SaeWs& ws, const uint32_t* cnt, float* scalars, int N) {
+    return ScanRole{cnt, (uint32_t*)(wsb + ws.offs), (uint32_t*)(wsb + ws.n_long), d.d_sae, scalars, (float)N};
+}
+
 }  // namespace
+
+// One launch of sae_decode_kernel (sae.hip): decode + LN-out + loss terms + dY + dh of N tokens of k slots, one wave per token.  A
+// caller sets the fields it means.
+struct SaeDecode {
+    int mode = 0;                            // 0: the whole thing; the feature-parallel step cuts it at the reconstruction -- 1: this rank's
+                                             // partial sum_s val_s W_dec[idx_s] only, written to sae_out (no b_dec, no LN-out); 2: everything
+                                             // behind it
+    int N = 0, d = 0, k = 0;                 // tokens, d_in, slots per token (pv_sae_relu_step: the per-token capacity)
+    const float* x = nullptr;                // what the loss is taken against (a transcoder, pv_sae_state.tc: the TARGET)
+    const float* W_dec = nullptr;
+    const float* b_dec = nullptr;            // (a transcoder: b_dec_out)
+    const int32_t* idx = nullptr;            // the kept features ...
+    const float* val = nullptr;              // ... and activations; <= 0: a hole (no gather, dh = 0)
+    const float* mu = nullptr;               // LN-out: out = (reconstruction + b_dec) * sd + mu
+    const float* sd = nullptr;
+    const float* norm = nullptr;             // the loss normaliser ||x_n - mean_batch(x)||_2
+    float* sae_out = nullptr;                // optional (mode 1: the partial sums)
+    float* dY = nullptr;                     // with dh, the gradients; NULL: none are wanted (inference)
+    float* dh = nullptr;                     // [N k] the gradient at the kept activations
+    float* loss_part = nullptr;              // [N] per-token loss terms
+    float grad_scale = 0.f;                  // 2 / (N_global * d_in)
+    const float* inv_norm = nullptr;         // set_decoder_norm_to_unit_norm is pending: W_dec still holds the un-normalised rows and row j
+                                             // stands for W_dec[j] * inv_norm[j] (the Adam kernel writes the normalised + updated row; see
+                                             // pv_sae_step)
+    const float* pre_sum = nullptr;          // mode 2: [N, d_in] the reconstruction summed over the ranks (without b_dec)
+    const float* addend = nullptr;           // mode 0, a transcoder: the skip term x_in @ W_skip^T the reconstruction starts from
+    float dh_add = 0.f;                      // pv_sae_relu_step: l1_coefficient / N_global, the L1 term's gradient on every kept activation
+                                             // (sae.py:617-626)
+    const uint32_t* tok_cnt = nullptr;       // pv_sae_relu_step: tok_cnt[n] = the pairs token n holds (front-packed; the rest of the row are holes)
+    const uint32_t* gate = nullptr;          // pv_sae_relu_step: the step's mode word -- nonzero = the step runs on the dense GEMMs, leave at once
+    ScanRole scan = {};                      // sae_scan_role: the launch carries one more workgroup, which runs the CSR scan (modes 0 and 2)
+};
+int sae_decode(const SaeDecode& a, hipStream_t stream);
 #endif

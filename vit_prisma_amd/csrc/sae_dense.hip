@@ -327,8 +327,8 @@ int dense_step_body(pv_sae_plan* plan, pv_sae_state* st, const float* x, int32_t
 // gb_dec = colsum(dY) - W_enc gb_enc (a transcoder: its two bias gradients, then gW_skip), from ws.dY and gb_enc of whichever form ran
 int dense_bias_grads(const pv_sae_desc& d, const pv_sae_state* st, const float* x, int N, unsigned char* wsb, const SaeWs& ws, hipStream_t stream) {
     const float* dY = (const float*)(wsb + ws.dY);
-    if (!sae_is_tc(st)) return sae_gbdec(d, st, dY, N, wsb, ws, stream);
-    const int rc = sae_tc_bias_grads(d, st, dY, N, wsb, ws, stream);
+    if (!sae_is_tc(st)) return sae_gbdec(d, st, dY, N, wsb, ws, stream, SAE_DY_TO_GB_DEC);
+    const int rc = sae_gbdec(d, st, dY, N, wsb, ws, stream, SAE_DY_TO_GB_DEC_OUT);
     return rc ? rc : sae_tc_skip_backward(d, st, x, dY, N, stream);
 }
 

@@ -2,7 +2,7 @@
 // Gated SAE step (GatedSparseAutoencoder, sae.py:648-792; pv_sae_gated).  hs [2N][F]: rows [0, N) feature_acts (later dM, then
 // dP), rows [N, 2N) relu(gate pre-activation) (later dG); dYs [2N][D]: rows [0, N) dY of the reconstruction, rows [N, 2N)
 // d aux / d (reconstruction through the gate).  Stacking the two row sets makes the two decoder products one GEMM, and
-// gW_dec = f^T dY + relu(gate)^T dVia one GEMM over K = 2N (sae_dense_gemm.hip).  The sparse form: below; the top-k form: sae.hip.
+// gW_dec = f^T dY + relu(gate)^T dVia one GEMM over K = 2N (sae_dense_gemm.hip).  The sparse form: below; the top-k form: sae_gated_topk.hip.
 // ------------------------------------------------------------------------------------------------
 #include <algorithm>
 #include "sae_bwd.hpp"
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void gated_axpy_kernel(float* __restrict__ y, 
 int sae_gated_gbdec(const pv_sae_desc& d, const pv_sae_state* st, const float* dYs, int N, float* tmpd, float* cspart, unsigned char* wsb,
                     const SaeWs& ws, hipStream_t stream) {
     const int D = d.d_in;
-    int rc = sae_gbdec(d, st, dYs, N, wsb, ws, stream);                   // colsum(dY) - W_enc gb_enc (= colsum(dP) for now)
+    int rc = sae_gbdec(d, st, dYs, N, wsb, ws, stream, SAE_DY_TO_GB_DEC);                  // colsum(dY) - W_enc gb_enc (= colsum(dP) for now)
     if (rc) return rc;
     rc = sae_colsum(dYs + (size_t)N * D, N, D, tmpd, 2.0f, cspart, stream);
     if (rc) return rc;

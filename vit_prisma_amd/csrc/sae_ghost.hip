@@ -263,7 +263,7 @@ extern "C" int pv_sae_topk_ghost(pv_sae_plan* plan, pv_sae_state* st, const floa
         hipLaunchKernelGGL(ghost_scatter_add_vec_kernel, dim3((nd + 255) / 256), dim3(256), 0, stream, st->gb_enc, ghost->dead_idx, nd,
                            (const float*)(gwb + gw.vec_b));
         PV_LAUNCH_CHECK("ghost scatter kernels");
-        rc = tc ? sae_tc_bias_grads(d, st, dY, N, wsb, ws, stream) : sae_gbdec(d, st, dY, N, wsb, ws, stream);
+        rc = sae_gbdec(d, st, dY, N, wsb, ws, stream, tc ? SAE_DY_TO_GB_DEC_OUT : SAE_DY_TO_GB_DEC);
         if (rc) return rc;
     }
     plan->live_offs = nullptr;
