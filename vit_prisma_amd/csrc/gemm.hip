@@ -802,6 +802,61 @@ __device__ __forceinline__ void epi8_bf16(const float4& x0, const float4& x1, co
 //     * MB = 5 makes M = 25600 (512 images x 50 tokens) exactly 80 row tiles: the N = 768 GEMMs (O-projection,
 //       MLP-2) are 240 tiles = ONE round of the 256 CUs, the QKV GEMM 720 = three
 // ---------------------------------------------------------------------------------------------------
+// The RESIDUAL PARK of the full-line form (LP = 2, EPI = RESID; -DPV_GEMM_RESID_PARK=0 builds the form without it).  The store
+// epilogue used to load the residual rows of blocks 1 .. MB-1 behind the stores of the block before; vmcnt retires in issue order,
+// so every wait for a row was a wait for two store streams to leave the CU while 240 CUs stored at once.  The full-line loop
+// already issues 3 * MB + 4 DEAD pieces per wave off its end (the A and B pieces of slab nk2, the A pieces of slab nk2 + 1), counted
+// in its waits; here those pieces fetch this wave's residual chunks instead -- for (block mi >= 1, pass it) lane l the 16 bytes it
+// would have loaded into e_res[mi][it] -- into ring slots the loop has freed, 1 KiB per piece, lane l at byte 16 l.  The epilogue
+// reads its chunk back with one ds_read_b128 from where the same lane's DMA put it and contains no load at all.
+//   park piece i = (mi - 1) * 4 + it, NPARK = 4 * (MB - 1) per wave.  Slab nk2 would have gone to slot P = nk2 & 1, which is free
+//   from the barrier of step nk2 - 2 on: its MB + 4 dead pieces per wave (8 waves x (MB + 4) KiB = the whole slot) take park pieces
+//   0 .. MB + 3 at  (wave * NP0 + i) KiB.  The A pieces of slab nk2 + 1 go out behind the LAST barrier of the loop into the other
+//   slot, free from there on: park pieces NP0 .. at  (wave * NP1 + i - NP0) KiB, and the 2 * MB - 8 that are left (two at MB = 5,
+//   none at MB = 4) are issued directly behind the loop, in front of the first store.  K of one or two slabs needs nothing else: the
+//   prologue's A pieces of slab 1 are the dead pieces of slab nk2 when nk2 = 1 and go through the same functor.
+//   Only the issuing wave reads a parked piece, behind its own vmcnt(0): no barrier.  The fp32 transposition leaves the ring for
+//   2 KB per wave beside it (8 rows per pass, as gemm_kernel_v8): 2 * 72 + 16 KB = the CU's 160 KB at MB = 5.
+//   The source is a descriptor over THIS WAVE's rows and columns of the residual (base at its first row / column, range ending
+//   with its last real row's last real column): rows >= M zero-fill; a chunk at columns >= N of a row that is not the last reads
+//   bytes of the residual buffer between that row and the next, and is never used (e_rows_left = 0 for such a lane).
+//   resid may be out1 (the plan never does that: vit_plan.hip adds resid_pre into resid_mid and resid_mid into resid_post, three
+//   buffers): a tile parks only rows and columns that it alone stores, and all of them before its first store.
+#ifndef PV_GEMM_RESID_PARK
+#define PV_GEMM_RESID_PARK 1
+#endif
+template <int MB, class R128>
+struct ResidParkSrc {
+    static constexpr int NPARK = 4 * (MB - 1), NP0 = MB + 4, NP1 = NPARK - NP0, NLOOP = NP0 + MB;   // NLOOP .. NPARK-1: behind the loop
+    static_assert(NP0 * 8 * 1024 == R128::SLOT && NP1 >= 0 && NP1 * 8 * 1024 <= R128::SLOT && NLOOP <= NPARK, "park geometry");
+    __amdgpu_buffer_rsrc_t rsR;
+    unsigned pA0, pB0, strideA, strideB, lpR, ldrB;
+    int nk2, wave;
+    // uniform source term / destination (bytes into its slot) of park piece i
+    __device__ static __forceinline__ constexpr int park_row(int i) { return (1 + (i >> 2)) * 32 + epi_pass_row<S16>(i & 3); }
+    __device__ __forceinline__ unsigned park_u(int i) const { return (unsigned)park_row(i) * ldrB; }
+    __device__ __forceinline__ int park_dst(int i) const { return i < NP0 ? (wave * NP0 + i) * 1024 : (wave * NP1 + (i - NP0)) * 1024; }
+    // piece j of slab kt into the slot: the operand piece, or off the end of K (every condition uniform, selects only) park piece
+    // j of slab nk2's MB + 4, NP0 + j of slab nk2 + 1's MB
+    __device__ __forceinline__ void piece(const R128& g, const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB,
+                                          unsigned char* slotA, unsigned char* slotB, int kt, int j) const {
+        const bool dead = kt >= nk2, second = kt > nk2;
+        // (the row constant and the wave's base are selected, then scaled: products selected instead are one loop-invariant scalar
+        // register per piece, and the MB = 4 instance runs out of them)
+        const int i1 = NP0 + j < NPARK ? NP0 + j : NPARK - 1;      // (in range where it is not used: B pieces are never `second`)
+        const unsigned pu = (unsigned)(second ? park_row(i1) : park_row(j)) * ldrB;
+        const int pd = ((second ? wave * NP1 : wave * NP0) + j) * 1024;
+        const unsigned kbase = (unsigned)kt * 128u;
+        if (j < MB) {
+            const unsigned off = (dead ? lpR : pA0) + (dead ? pu : (unsigned)j * strideA + kbase);
+            kloop::dma16(dead ? rsR : rsA, slotA + (dead ? pd : (j * 8 + wave) * 1024), off);
+        } else {
+            const unsigned off = (dead ? lpR : pB0) + (dead ? pu : (unsigned)(j - MB) * strideB + kbase);
+            kloop::dma16(dead ? rsR : rsB, slotB + (dead ? pd : R128::B_BASE + ((j - MB) * 8 + wave) * 1024), off);
+        }
+    }
+};
+
 template <typename T, int MB, int EPI, int ACT, int LP = 0>
 __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
     static_assert(sizeof(T) == 2, "v7 is the bf16 kernel");
@@ -809,6 +864,10 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
     using R128 = kloop::Ring128<MB, false, S16>;
     constexpr int TM = 64 * MB, TN = 256, SLOT = R64::SLOT, NA = R64::NA;
     static_assert(R128::SLOT == 2 * SLOT, "a full-line slot is two 64-byte-slab slots");
+    constexpr bool PARK = PV_GEMM_RESID_PARK && LP == 2 && EPI == PV_EPI_RESID;
+    using Park = ResidParkSrc<MB, R128>;
+    __shared__ __attribute__((aligned(16))) unsigned char stage[PARK ? 8 * 2048 : 16];      // (PARK: the epilogue's transposition)
+    static_assert(!PARK || 4 * SLOT + 8 * 2048 <= 160 * 1024, "one workgroup per CU");
     // the ring slots, one object each (kloop.hpp).  LP >= 2 (full-line form): two slots of 128-byte rows in ring0 / ring1, the other
     // objects shrink to stubs
     __shared__ __attribute__((aligned(16))) unsigned char ring0[LP >= 2 ? 2 * SLOT : SLOT];
@@ -851,7 +910,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
     const int e_lrow = epi_lane_row<S16>(lane);
     const int e_rows_left = e_live ? p.M - (m0 + wm * 32 * MB + e_lrow) : 0;    // row mi*32 + pass_row(it) of this lane is real iff < e_rows_left
     uint4 e_bias = make_uint4(0, 0, 0, 0);
-    constexpr int NRES = EPI == PV_EPI_RESID ? MB : 1;
+    constexpr int NRES = EPI == PV_EPI_RESID && !PARK ? MB : 1;      // (PARK: block 0 in registers, the others in LDS)
     uint4 e_res[NRES][4];
 #pragma unroll
     for (int mi = 0; mi < NRES; ++mi)
@@ -948,10 +1007,27 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
             if (j < MB) return dead ? kloop::DEAD : pA0 + ((unsigned)j * strideA + kbase);
             return dead ? kloop::DEAD : pB0 + ((unsigned)(j - MB) * strideB + kbase);
         };
-        KLOOP_RUN_FULL_LINE(kloop::Bf16, MB, acc, g, rsA, rsB, ring0, ring1, nk2, src);
+        if constexpr (PARK) {
+            // the same pieces, and off the end of K the residual park (see ResidParkSrc)
+            (void)src;
+            const int r_row0 = m0 + wm * 32 * MB, r_col0 = n0 + wn * 64;
+            const int r_rows = min(max(p.M - r_row0, 0), 32 * MB), r_cols = min(max(p.N - r_col0, 0), 64);
+            const unsigned ldrB = (unsigned)p.ldr * EB;
+            const unsigned r_bytes = (r_rows > 0 && r_cols > 0) ? (unsigned)(r_rows - 1) * ldrB + (unsigned)r_cols * EB : 0u;
+            const unsigned char* r_base = reinterpret_cast<const unsigned char*>(p.resid) + ((int64_t)r_row0 * p.ldr + r_col0) * EB;
+            const Park park{__builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(r_base), 0, (int)r_bytes, 0x00020000),
+                            pA0, pB0, strideA, strideB, (unsigned)e_lrow * ldrB + (unsigned)(lane & 7) * 16u, ldrB, nk2, wave};
+            KLOOP_RUN_FULL_LINE(kloop::Bf16, MB, acc, g, rsA, rsB, ring0, ring1, nk2, park);
+            // what the loop's dead pieces did not take, into the slot its last barrier freed
+            unsigned char* const slot1 = (nk2 & 1) ? ring0 : ring1;
+#pragma unroll
+            for (int i = Park::NLOOP; i < Park::NPARK; ++i) kloop::dma16(park.rsR, slot1 + park.park_dst(i), park.lpR + park.park_u(i));
+        } else {
+            KLOOP_RUN_FULL_LINE(kloop::Bf16, MB, acc, g, rsA, rsB, ring0, ring1, nk2, src);
+        }
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0): drain the off-the-end prefetches
-    __syncthreads();
+    __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0): drain the off-the-end prefetches (PARK: this wave's parked rows have landed)
+    if constexpr (!PARK) __syncthreads();   // (PARK: the epilogue touches nothing another wave reads or writes)
     trace_stamp(p.trace, bid, 1);
 #ifdef PV_TUNING
     if (p.dbg & 2) {
@@ -961,12 +1037,48 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
 #endif
 
     constexpr int CLD = 64;
-    float* Cs = reinterpret_cast<float*>((wave < 4 ? ring0 : ring1) + (wave & 3) * (32 * CLD * 4));
+    [[maybe_unused]] float* Cs = reinterpret_cast<float*>((wave < 4 ? ring0 : ring1) + (wave & 3) * (32 * CLD * 4));
     const pv_f32x2 e_b[4] = {unpack2(e_bias.x), unpack2(e_bias.y), unpack2(e_bias.z), unpack2(e_bias.w)};
     const int64_t e_row0 = (int64_t)(m0 + wm * 32 * MB + e_lrow) * p.ldo;
     T* const o0_base = e_out0 ? e_out0 + e_row0 + e_col : nullptr;
     T* const o1_base = reinterpret_cast<T*>(p.out1) + e_row0 + e_gn;
-    const float* Cr = Cs + epi_read_off<S16>(lane);
+    [[maybe_unused]] const float* Cr = Cs + epi_read_off<S16>(lane);
+    if constexpr (PARK) {
+        // a store stream with no load in it: 8 rows x 64 columns per pass through the wave's own 2 KB (the ring holds the parked
+        // rows), the residual chunk of blocks >= 1 from where this lane's DMA put it
+        float* const Cs8 = reinterpret_cast<float*>(stage + wave * 2048);
+        const float* const Cr8 = Cs8 + epi_read_off<S16>(lane);
+        [[maybe_unused]] float* const Cw8 = Cs8 + half * 256 + l31;
+        const unsigned char* const slot0 = (Kb / 128 & 1) ? ring1 : ring0;
+        const unsigned char* const slot1 = (Kb / 128 & 1) ? ring0 : ring1;
+        const unsigned char* const pk0 = slot0 + (wave * Park::NP0) * 1024 + lane * 16;
+        const unsigned char* const pk1 = slot1 + (wave * Park::NP1) * 1024 + lane * 16;
+#pragma unroll
+        for (int mi = 0; mi < MB; ++mi) {
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                if constexpr (S16) {
+                    stage_pass16(Cs8, acc[mi], it, lane);
+                } else {
+#pragma unroll
+                    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) Cw8[j * 64 + ni * 32] = acc[mi][ni][4 * it + j];
+                }
+                __builtin_amdgcn_wave_barrier();
+                if (mi * 32 + epi_pass_row<S16>(it) < e_rows_left) {
+                    const float4 x0 = *reinterpret_cast<const float4*>(Cr8);
+                    const float4 x1 = *reinterpret_cast<const float4*>(Cr8 + 4);
+                    const int i = mi > 0 ? (mi - 1) * 4 + it : 0;
+                    const uint4 res = mi == 0 ? e_res[0][it]
+                                              : *reinterpret_cast<const uint4*>(i < Park::NP0 ? pk0 + i * 1024 : pk1 + (i - Park::NP0) * 1024);
+                    const int64_t ro = (int64_t)(mi * 32 + epi_pass_row<S16>(it)) * p.ldo;
+                    epi8_bf16<EPI, ACT>(x0, x1, e_b, o0_base ? o0_base + ro : nullptr, o1_base + ro, res);
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+    } else {
 #pragma unroll
     for (int mi = 0; mi < MB; ++mi) {
         if constexpr (S16) {
@@ -998,6 +1110,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v7(const GemmParams p) {
             }
         }
         __builtin_amdgcn_wave_barrier();
+    }
     }
 #undef PV_V7_FETCH_RES
     trace_stamp(p.trace, bid, 2);
@@ -1331,7 +1444,9 @@ int dispatch(GemmParams& p, hipStream_t stream) {
             // 128 x 128 tiles, 3 workgroups / CU (v4) or one 8-wave workgroup with a (64*MB) x 256 tile (v7);
             // history and measurements of the variants in between: profiles/r01_notes.md
             if constexpr (EB == 2) {
-                if (p.vec_out && p.N % 8 == 0) {
+                // (the residual park addresses a wave's 160 residual rows with 32-bit offsets)
+                const bool r_ok = p.epi != PV_EPI_RESID || (uint64_t)p.ldr * EB * 320 < 0xffffff00ull;
+                if (p.vec_out && p.N % 8 == 0 && r_ok) {
                     const int pick = pick_v7(p);
                     if (pick == 5) return launch_v7<T, 5>(p, stream);
                     if (pick == 4) return launch_v7<T, 4>(p, stream);

@@ -108,6 +108,22 @@ __device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t& rs, unsigned
 }
 __device__ __forceinline__ void pin() { __builtin_amdgcn_sched_barrier(0); }
 
+// One piece of a full-line slab through the source functor.  A functor is  src(kt, j) -> offset  and the piece goes where
+// Ring128::issue puts it; one that has a member  piece(g, rsA, rsB, slotA, slotB, kt, j)  places the piece itself -- descriptor,
+// source and destination inside the slot it is handed (gemm.hip's residual park: the DEAD pieces off the end of the loop get a real
+// source there).  Same rules: selects only, and the destination stays inside the slot object of the call.
+template <class G, class Src>
+__device__ __forceinline__ auto issue_piece(int, const G& g, const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB,
+                                            unsigned char* slotA, unsigned char* slotB, int kt, int j, const Src& src)
+    -> decltype(src.piece(g, rsA, rsB, slotA, slotB, kt, j)) {
+    return src.piece(g, rsA, rsB, slotA, slotB, kt, j);
+}
+template <class G, class Src>
+__device__ __forceinline__ void issue_piece(long, const G& g, const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB,
+                                            unsigned char* slotA, unsigned char* slotB, int kt, int j, const Src& src) {
+    g.issue(rsA, rsB, slotA, slotB, j, src(kt, j));
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Tile order.  Block b of a launch runs on XCD b % 8: xcd_run() is the bijection that gives each XCD a contiguous run of the
 // linear order, so that neighbours in that order share an L2.  (A persistent kernel passes its virtual block id and the tile
@@ -436,11 +452,11 @@ struct Ring128 {
     __device__ __forceinline__ void prologue(const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB, unsigned char* a0,
                                              unsigned char* b0, unsigned char* a1, unsigned char* b1, const Src& src) const {
 #pragma unroll
-        for (int j = 0; j < NPIECE; ++j) issue(rsA, rsB, a0, b0, j, src(0, j));
+        for (int j = 0; j < NPIECE; ++j) issue_piece(0, *this, rsA, rsB, a0, b0, 0, j, src);
         __builtin_amdgcn_s_waitcnt(0x0F70);
         __builtin_amdgcn_s_barrier();
 #pragma unroll
-        for (int j = 0; j < MB; ++j) issue(rsA, rsB, a1, b1, j, src(1, j));
+        for (int j = 0; j < MB; ++j) issue_piece(0, *this, rsA, rsB, a1, b1, 1, j, src);
     }
 };
 
@@ -471,10 +487,10 @@ __device__ __forceinline__ void step_full_line(f32x16 (&acc)[MB][2], uint4 (&fa)
                 fb[(h + 1) & 1][0] = h < 3 ? g.rd_b(curB, h < 3 ? h + 1 : 0, 0) : g.rd_b(nxtB, 0, 0);
                 fb[(h + 1) & 1][1] = h < 3 ? g.rd_b(curB, h < 3 ? h + 1 : 0, 1) : g.rd_b(nxtB, 0, 1);
             }
-            if (h == 3) g.issue(rsA, rsB, curA, curB, mi, src(kt + 2, mi));
+            if (h == 3) issue_piece(0, g, rsA, rsB, curA, curB, kt + 2, mi, src);
             if (h == 0) {
 #pragma unroll
-                for (int jb = mi; jb < 4; jb += MB) g.issue(rsA, rsB, nxtA, nxtB, MB + jb, src(kt + 1, MB + jb));
+                for (int jb = mi; jb < 4; jb += MB) issue_piece(0, g, rsA, rsB, nxtA, nxtB, kt + 1, MB + jb, src);
             }
             pin();
         }
@@ -507,10 +523,10 @@ __device__ __forceinline__ void step_full_line(f32x16 (&acc)[MB][2], uint4 (&fa)
 #pragma unroll
                 for (int ni = 0; ni < 4; ++ni) fb[ni >> 1][ni & 1] = q == 1 ? g.rd_b16(curB, 1, ni) : g.rd_b16(nxtB, 0, ni);
             }
-            if (q == 3) g.issue(rsA, rsB, curA, curB, mi, src(kt + 2, mi));
+            if (q == 3) issue_piece(0, g, rsA, rsB, curA, curB, kt + 2, mi, src);
             if (q == 0) {
 #pragma unroll
-                for (int jb = mi; jb < 4; jb += MB) g.issue(rsA, rsB, nxtA, nxtB, MB + jb, src(kt + 1, MB + jb));
+                for (int jb = mi; jb < 4; jb += MB) issue_piece(0, g, rsA, rsB, nxtA, nxtB, kt + 1, MB + jb, src);
             }
             pin();
         }
