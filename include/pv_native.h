@@ -336,7 +336,9 @@ int pv_prof_read_tag(int32_t kind, int32_t tag, int64_t* launches, double* total
 
 /* Debug only (tools/gemm_trace.py): per-workgroup phase stamps {t_start, t_loop_end, t_end, hw_id} (100 MHz wall
  * clock) of the launch_idx-th plain GEMM launch from now; read blocks until the device is idle.
- * info6 = {M, N, K, epilogue, n_workgroups, kernel id}.  NOT part of the product path: the first arm hipMalloc's a
+ * info6 = {M, N, K, epilogue, n_workgroups, kernel id}, from the same decision that launched (csrc/gemm.hip, choose()): kernel id
+ * 70 + MB for gemm_kernel_v7 / v8 on (64 MB) x 256 tiles (v8: one row of stamps per tile), 4 for gemm_kernel_v4, 1 for gemm_kernel,
+ * which writes no stamps (n_workgroups 0, nothing copied out).  NOT part of the product path: the first arm hipMalloc's a
  * 256 KB device buffer owned by the library (the one place it allocates device memory) and hipMemset's it. */
 int pv_debug_gemm_trace_arm(int32_t launch_idx);
 int pv_debug_gemm_trace_read(uint64_t* host_out, int32_t max_wg, int32_t* info6);

@@ -422,7 +422,7 @@ def _rcp(t, flush):
 
 
 def act_twin(act, x, bug=None, flush=False):
-    """float32 twin of act2<ACT> (csrc/gemm.hip) with an exact exp2 and reciprocal in place of v_exp_f32 / v_rcp_f32; ``flush``: both
+    """float32 twin of act2<ACT> (csrc/gemm_epi.hpp) with an exact exp2 and reciprocal in place of v_exp_f32 / v_rcp_f32; ``flush``: both
     return 0 for a denormal result, as the hardware instructions may.  x: a float32 tensor; returns float32 (unrounded).  ``bug``: one
     of ACT_BUGS, a twin that is wrong on purpose."""
     assert bug is None or bug in ACT_BUGS

@@ -1,6 +1,6 @@
 """The lane maps of the bf16 GEMMs on v_mfma_f32_16x16x32_bf16, emulated in numpy (no GPU).
 
-csrc/kloop.hpp and csrc/gemm.hip state where a DMA piece lands in an LDS slot (swz64 / swz128), which 16 bytes a lane reads as its
+csrc/kloop.hpp and the GEMM kernel files (csrc/gemm_tiled.hpp, csrc/gemm_v4.hpp, csrc/gemm_epi.hpp) state where a DMA piece lands in an LDS slot (swz64 / swz128), which 16 bytes a lane reads as its
 A / B fragment, which accumulator registers a 16 x 16 block of the wave's tile occupies, and how the store epilogue walks a 32-row
 block in four passes through its 8 x 64 staging rows.  This file restates those formulas and runs one slab of a (64*MB) x 256 tile
 through them -- every wave, every lane -- for Ring64 and Ring128 at MB = 4 and 5: the tile must come out as A . B^T with every

@@ -1,4 +1,4 @@
-"""The bf16 GEMM kernels on v_mfma_f32_16x16x32_bf16 (csrc/kloop.hpp, csrc/gemm.hip): fragment and accumulator lane maps, and that
+"""The bf16 GEMM kernels on v_mfma_f32_16x16x32_bf16 (csrc/kloop.hpp, csrc/gemm_tiled.hpp, csrc/gemm_v4.hpp): fragment and accumulator lane maps, and that
 every kernel / K-loop form accumulates alike.
 
 All through pv_gemm_epilogue with the kernel forced by the tuning overrides, on the smallest shapes that cross every boundary:

@@ -1,4 +1,4 @@
-"""The residual park of the full-line GEMM (csrc/gemm.hip, ResidParkSrc): gemm_kernel_v7<bf16, MB, RESID, 0, 2> fetches the residual
+"""The residual park of the full-line GEMM (csrc/gemm_tiled.hpp, ResidParkSrc): gemm_kernel_v7<bf16, MB, RESID, 0, 2> fetches the residual
 rows of its blocks 1 .. MB-1 with the DMA pieces that run off the end of its K loop, into LDS, and its store epilogue reads each
 16-byte chunk back from where the same lane's DMA put it.
 
@@ -141,3 +141,85 @@ def test_the_forced_launch_is_the_full_line_v7_kernel(tuning):
         tuning("reset")
         assert info.tolist() == [M, N, K, 2, tiles, 70 + tile]
         assert (buf[:tiles, 2] > buf[:tiles, 1]).all() and (buf[:tiles, 1] > buf[:tiles, 0]).all()
+
+
+# ---- the trace describes the launch that happened: its info comes from the choice that launched (csrc/gemm.hip, choose()), also
+# ---- where the forced tile is not what the launch can take
+
+def _traced(tuning, keys, A, B, bias, res, lda, ldr, M, N, K, rows_alloc=648):
+    """One armed launch under the tuning keys: (out0, out1, the first 64 rows of the trace buffer, info)."""
+    L = _native.lib()
+    L.pv_debug_gemm_trace_arm.argtypes = [ctypes.c_int32]
+    L.pv_debug_gemm_trace_read.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    st = torch.cuda.current_stream().cuda_stream
+    o0 = torch.full((rows_alloc, N), GUARD, device="cuda", dtype=torch.bfloat16)
+    o1 = torch.full((rows_alloc, N), GUARD, device="cuda", dtype=torch.bfloat16)
+    tuning("reset")
+    for key, value in keys.items():
+        tuning(key, value)
+    assert L.pv_debug_gemm_trace_arm(0) == 0
+    rc = L.pv_gemm_epilogue(1, 2, 0, A.data_ptr(), lda, B.data_ptr(), lda, bias.data_ptr(), res.data_ptr(), ldr,
+                            o0.data_ptr(), o1.data_ptr(), N, M, N, K, st)
+    buf = np.zeros((64, 4), np.uint64)
+    info = np.zeros(6, np.int32)
+    rc_read = L.pv_debug_gemm_trace_read(buf.ctypes.data, 64, info.ctypes.data)
+    tuning("reset")
+    _native.check(rc, "pv_gemm_epilogue")
+    assert rc_read == 0
+    return o0, o1, buf, info.tolist()
+
+
+def _stamped_in_order(rows):
+    return bool(((rows[:, 2] > rows[:, 1]) & (rows[:, 1] > rows[:, 0]) & (rows[:, 0] > 0)).all())
+
+
+def test_trace_of_a_forced_tile_that_falls_back_to_v4(tuning):
+    """ldr = N + 4: the residual's rows are no 16-byte multiples, the vector epilogue is not legal and the launch is gemm_kernel_v4's
+    on 3 x 3 tiles of 128 x 128, whatever gemm_tile says -- and that is what the trace must say (it used to say kernel 75 on 4
+    workgroups, and the 8192-row guard was applied to that count)."""
+    M, N, K = 353, 264, 192
+    A, B, bias, _ = _operands(N, K)
+    A = A[:M].contiguous()
+    res = _planted_residual(M, N, N + 4, 648)
+    o0, o1, buf, info = _traced(tuning, {"gemm_tile": 5, "gemm_persist": 0}, A, B, bias, res, K, N + 4, M, N, K)
+    print("info", info, "rows stamped", int((buf[:, 0] > 0).sum()))
+    assert info == [M, N, K, 2, 3 * 3, 4]
+    assert _stamped_in_order(buf[:9]), buf[:9]
+    assert not buf[9].any(), buf[9]
+    tuning("gemm_tile", 0)
+    v0, v1 = _launch(A, B, bias, res, N + 4, M, N, K, 648)
+    tuning("reset")
+    for got, ref, name in ((o0, v0, "out0"), (o1, v1, "out1")):
+        assert bool((_bits(got) == _bits(ref)).all()), name
+
+
+def test_trace_of_a_launch_that_falls_back_to_gemm_kernel(tuning):
+    """K = 100, lda = ldb = 100: 200-byte operand rows are not 16-byte legal, the launch is gemm_kernel's, which writes no stamps:
+    kernel 1, no workgroups, nothing in the buffer (the info used to describe a v7 launch, and the zeros read as its trace)."""
+    M, N, K = 353, 264, 100
+    g = torch.Generator(device="cuda").manual_seed(7100)
+    A = torch.randn(M, K, device="cuda", generator=g).bfloat16()
+    B = (torch.randn(N, K, device="cuda", generator=g) * (0.4 / K ** 0.5)).bfloat16()
+    bias = (torch.randn(N, device="cuda", generator=g) * 0.2).bfloat16()
+    pre = (A.double() @ B.double().T + bias.double()).float()
+    res = _planted_residual(M, N, N + 4, 648)
+    o0, o1, buf, info = _traced(tuning, {"gemm_tile": 5, "gemm_persist": 0}, A, B, bias, res, K, N + 4, M, N, K)
+    print("info", info)
+    assert info[:4] == [M, N, K, 2] and info[4] == 0 and info[5] == 1, info
+    assert not buf.any()
+    assert bool((o0[M:].float() == GUARD).all()) and bool((o1[M:].float() == GUARD).all())
+    for got, want, name in ((o0[:M], pre, "out0"), (o1[:M], o0[:M].float() + res[:M, :N].float(), "out1")):
+        worst = float(((got.float() - want).abs().amax(dim=1) / want.abs().amax(dim=1)).max())
+        print(name, "worst", worst)
+        assert worst < 2.0 ** -8, (name, worst)
+
+
+def test_trace_of_the_persistent_kernel(tuning):
+    """gemm_persist 1, four 128-byte slabs: gemm_kernel_v8, whose stamps are indexed by virtual block id -- one row per tile."""
+    M, N, K = 353, 264, 256
+    A, B, bias, _ = _operands(N, K)
+    res = _planted_residual(M, N, N + 24, 648)
+    _, _, buf, info = _traced(tuning, {"gemm_tile": 5, "gemm_persist": 1}, A[:M].contiguous(), B, bias, res, K, N + 24, M, N, K)
+    print("info", info)
+    assert info == [M, N, K, 2, 4, 75]
+    assert _stamped_in_order(buf[:4]), buf[:4]

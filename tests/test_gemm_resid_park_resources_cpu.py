@@ -1,7 +1,8 @@
-"""What the compiler makes of the residual park (csrc/gemm.hip, ResidParkSrc): the two instances that carry it,
+"""What the compiler makes of the residual park (csrc/gemm_tiled.hpp, ResidParkSrc): the two instances that carry it,
 gemm_kernel_v7<bf16, 5, RESID, 0, 2> and <bf16, 4, RESID, 0, 2>, held to the budget their design states.
 
-gemm.hip is compiled twice with build.py's flags and ``-Rpass-analysis=kernel-resource-usage``, as tests/test_kernel_resources_cpu.py
+The GEMM sources (gemm.hip, which includes gemm_v4.hpp and gemm_tiled.hpp, and gemm_generic.hip: all the kernels the one gemm.hip held) are compiled twice
+with build.py's flags and ``-Rpass-analysis=kernel-resource-usage``, as tests/test_kernel_resources_cpu.py
 does: as built, and with ``-DPV_GEMM_RESID_PARK=0``, which is the form before the park (tools/isa_vs_parent.py finds that build's
 kernels instruction for instruction those of the commit before: profiles/r18_resid_park_isa_vs_parent.txt).  The second build is where
 "the parent's figure" below is read from; at the time of writing it is 247 VGPRs (MB = 5) and 216 (MB = 4), the park's 240 and 205.
@@ -11,9 +12,9 @@ kernels instruction for instruction those of the commit before: profiles/r18_res
     2 waves per SIMD           one 512-thread workgroup per CU
     VGPRs <= the parent's      the park may cost no register (it frees the sixteen the rows of blocks 1 .. were loaded into)
 
-and every OTHER kernel of gemm.hip must report the same resources in both builds: the switch touches nothing else.
+and every OTHER kernel of the GEMM sources must report the same resources in both builds: the switch touches nothing else.
 
-Not ``gpu``-marked; skipped where no hipcc is found.  Two compilations of gemm.hip in parallel, about a minute.
+Not ``gpu``-marked; skipped where no hipcc is found.  Two compilations of each source, all in parallel, about a minute.
 """
 from __future__ import annotations
 
@@ -41,11 +42,15 @@ _FIELDS = {
 }
 
 
-def _report(hipcc, outdir, tag, extra):
-    cmd = [hipcc, *pv_build.FLAGS, *extra, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(pv_build.CSRC, "gemm.hip"),
-           "-o", os.path.join(outdir, f"gemm_{tag}.o")]
+# every GEMM source
+SOURCES = tuple(s for s in pv_build.sources() if s.startswith("gemm"))
+
+
+def _report(hipcc, outdir, tag, extra, src):
+    cmd = [hipcc, *pv_build.FLAGS, *extra, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(pv_build.CSRC, src),
+           "-o", os.path.join(outdir, f"{src[:-4]}_{tag}.o")]
     r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, f"hipcc failed ({tag}):\n{r.stderr[-4000:]}"
+    assert r.returncode == 0, f"hipcc failed ({src}, {tag}):\n{r.stderr[-4000:]}"
     out, cur = {}, None
     for line in r.stderr.splitlines():
         m = re.search(r"remark: Function Name: (\S+)", line)
@@ -55,6 +60,19 @@ def _report(hipcc, outdir, tag, extra):
         m = re.search(r"remark:\s+([A-Za-z][^:]*): (\d+) \[-Rpass-analysis", line)
         if m and cur is not None and m.group(1) in _FIELDS:
             cur[_FIELDS[m.group(1)]] = int(m.group(2))
+    return out
+
+
+def _reports(ex, hipcc, outdir, tag, extra):
+    return [ex.submit(_report, hipcc, outdir, tag, extra, src) for src in SOURCES]
+
+
+def _merged(futures, tag):
+    out = {}
+    for f in futures:
+        part = f.result()
+        assert not set(part) & set(out), f"a kernel in two sources ({tag}): {sorted(set(part) & set(out))}"
+        out.update(part)
     assert out, f"hipcc printed no kernel-resource-usage remarks ({tag})"
     return out
 
@@ -66,10 +84,11 @@ def builds(tmp_path_factory):
     except RuntimeError:
         pytest.skip("no hipcc: the resource report needs the ROCm compiler")
     outdir = str(tmp_path_factory.mktemp("resid_park_resources"))
-    with cf.ThreadPoolExecutor(max_workers=2) as ex:
-        park = ex.submit(_report, hipcc, outdir, "park", [])
-        parent = ex.submit(_report, hipcc, outdir, "parent", ["-DPV_GEMM_RESID_PARK=0"])
-        return park.result(), parent.result()
+    assert "gemm.hip" in SOURCES and "gemm_generic.hip" in SOURCES, SOURCES
+    with cf.ThreadPoolExecutor(max_workers=2 * len(SOURCES)) as ex:
+        park = _reports(ex, hipcc, outdir, "park", [])
+        parent = _reports(ex, hipcc, outdir, "parent", ["-DPV_GEMM_RESID_PARK=0"])
+        return _merged(park, "park"), _merged(parent, "parent")
 
 
 def _one(table, fragment):
@@ -97,6 +116,6 @@ def test_the_switch_touches_no_other_kernel(builds):
     park, parent = builds
     assert sorted(park) == sorted(parent)
     others = [k for k in park if not any(f in k for f in PARKED.values())]
-    assert len(others) == len(park) - 2 and len(others) > 20
+    assert len(others) == len(park) - 2 and len(others) == 59, len(others)      # (the kernels of all GEMM sources: 61)
     differ = {k: (parent[k], park[k]) for k in others if parent[k] != park[k]}
     assert not differ, differ

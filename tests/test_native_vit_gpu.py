@@ -775,7 +775,7 @@ def _digests(model, bs_list):
 def test_bf16_results_do_not_depend_on_the_gemm_kernel_or_the_batch_size(tuning):
     """At 77 and 300 images (partial row tiles in every GEMM) the three bf16 GEMM kernels -- 128 x 128 (v4), 256 x 256 and
     320 x 256 (v7) -- must give BIT-identical digests over all 214 cache tensors: they accumulate every output element
-    in the same K order and share one activation / rounding sequence (act_any in gemm.hip).  Consequence, checked last:
+    in the same K order and share one activation / rounding sequence (act_any in gemm_epi.hpp).  Consequence, checked last:
     an image's cache rows are the same bits at bs = 1 (v4 picked) and inside a 300-image batch (v7 picked)."""
     model, arch, _ = build("clip-vit-b32", torch.bfloat16)
     ref = None

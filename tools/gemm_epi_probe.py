@@ -27,6 +27,8 @@ for epi in ("bias", "act", "resid"):
         buf = np.zeros((8192, 4), np.uint64); info = np.zeros(6, np.int32)
         assert L.pv_debug_gemm_trace_read(buf.ctypes.data, 8192, info.ctypes.data) == 0
         n = int(info[4]); t = buf[:n].astype(np.int64); ok = t[:, 2] > 0
+        if not ok.any():      # (kernel 1 = gemm_kernel writes no stamps; or more workgroups than the trace buffer has rows)
+            print(f"{epi:5s} {M}x{Nn}x{K} kernel=v{info[5]}: this launch left no trace", flush=True); continue
         t0 = t[ok, 0].min()
         stt, le, en = (t[ok, 0] - t0) / 100.0, (t[ok, 1] - t0) / 100.0, (t[ok, 2] - t0) / 100.0
         loop, ep = le - stt, en - le

@@ -33,6 +33,8 @@ with torch.no_grad():
         assert L.pv_debug_gemm_trace_read(buf.ctypes.data, 8192, info.ctypes.data) == 0
         n = int(info[4]); t = buf[:n].astype(np.int64)
         ok = t[:, 2] > 0
+        if not ok.any():      # (kernel 1 = gemm_kernel writes no stamps; or more workgroups than the trace buffer has rows)
+            print(f"{names[j]:6s} M,N,K={info[0]},{info[1]},{info[2]} epi={info[3]} kernel=v{info[5]}: this launch left no trace"); continue
         t0 = t[ok, 0].min()
         st, le, en = (t[ok, 0] - t0) / 100.0, (t[ok, 1] - t0) / 100.0, (t[ok, 2] - t0) / 100.0     # us
         span = en.max()

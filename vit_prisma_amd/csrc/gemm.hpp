@@ -44,6 +44,7 @@ int pv_launch_gemm(int dtype, GemmParams p, hipStream_t stream);
 int pv_launch_act(int dtype, int act, const void* pre, void* post, int64_t n, hipStream_t stream);
 
 // debug: arm per-workgroup phase tracing for the `launch_idx`-th GEMM launch from now (0 = next), read it back
-// (blocks until the device is idle).  info = {M, N, K, epi, n_workgroups, kernel version}.
+// (blocks until the device is idle).  info = {M, N, K, epi, n_workgroups, kernel}: 70 + MB for v7 / v8, 4 for v4, 1 and no
+// workgroups for gemm_kernel, which writes no stamps (gemm.hip: the choice that launched is the one described).
 extern "C" int pv_debug_gemm_trace_arm(int32_t launch_idx);
 extern "C" int pv_debug_gemm_trace_read(uint64_t* host_out, int32_t max_wg, int32_t* info6);
