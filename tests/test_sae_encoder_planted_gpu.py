@@ -117,20 +117,26 @@ def test_step_with_the_inline_fallback_on_planted_rows(name, tuning):
     same_result(c, tw, (idx, val), (idx2, val2), f"step {name}: the second call")
 
 
-@pytest.mark.parametrize("name", ["edges", "band_inversion_64"])
+@pytest.mark.parametrize("name", ["edges", "band_inversion_64", "one_round"])
 def test_sample_pass_in_256_row_tiles_and_the_other_k_loops(name, tuning):
     """d_in 64 takes the sample pass in 128-row tiles by default; here the 256-row form, then the barrier-then-fetch and pipelined K loops
-    (HCAP is 4096 there, which no planted block of these cases reaches): every form gives the default's bits on decided tokens"""
+    (HCAP is 4096 there, which no planted block of these cases reaches), the per-block epilogue in the full-line loop (``enc_rounds``:
+    the case's own HCAP, a compaction round per 32-row block -- ``one_round`` is the planted shape that takes the one-round epilogue by
+    default, and the two forms share the wave scan) and the unfused pre-pass (``sae_fold`` 0: sae_wmax_kernel in a launch of its own,
+    the filter's form as by default): every form gives the default's bits on decided tokens"""
     c = EC.case(name)
     tw = EC.twin(c)
     other = copy.copy(c)
     other.hcap, other.one_round = 4096, False
-    tw_other = EC.twin(other)
-    assert tw_other["outcome"] == tw["outcome"] and "hcap?" not in tw["outcome"]
+    rounds = copy.copy(c)
+    rounds.one_round = False
+    for form in (other, rounds):
+        tw_other = EC.twin(form)
+        assert tw_other["outcome"] == tw["outcome"] and "hcap?" not in tw["outcome"]
     eng = engine(c)
     x = torch.from_numpy(c.x).cuda()
     idx0, val0 = (t.clone() for t in eng.encode_topk(x)[:2])
-    for key, value in (("enc_tm256", 1), ("gemm_loop", 0), ("gemm_loop", 1)):
+    for key, value in (("enc_tm256", 1), ("gemm_loop", 0), ("gemm_loop", 1), ("enc_rounds", 1), ("sae_fold", 0)):
         tuning(key, value)
         idx, val = (t.clone() for t in eng.encode_topk(x)[:2])
         n_fb = eng.fallback_rows()

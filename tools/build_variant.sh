@@ -5,6 +5,7 @@
 # PV_NATIVE_LIB=tools/variants/libpvnative_NAME.so
 # Switches of the ViT forward's kernels: -DPV_STORE_CONSUMED=P -DPV_STORE_TAP=P (store policy of the large outputs, P = 0 plain,
 # 1 nt, 2 sc1, 3 sc1 nt; pv_common.hpp: SRC="gemm gemm_generic rowops attention"), -DPV_ATTN_V_ROWS=0, -DPV_ATTN_VROWS_WAVES=3 (SRC=attention), -DPV_GEMM_MFMA=32 (the bf16 GEMMs v4 / v7 / v8 on v_mfma_f32_32x32x16_bf16 instead of 16x16x32; SRC=gemm is enough)
+# Switches of the filtered SAE encoder: -DPV_SEL_TRACE, -DPV_SEL_WAVES=N (SRC=sae_enc: the top-k select kernel's time stamps / launch bound), -DPV_ENC_TRACE (SRC="sae_enc sae_enc_gemm": the filter GEMM's time stamps), -DPV_DEC_ROWS=N (SRC=sae)
 # -DPV_GEMM_RESID_PARK=0 (gemm_kernel_v7's full-line residual instances without the residual park: the residual rows loaded inside the store epilogue; SRC=gemm is enough)
 set -e
 cd "$(dirname "$0")/.."

@@ -1,5 +1,5 @@
 """Per-workgroup timeline of the filter GEMM (sae_enc_gemm_kernel<1>: 1536 tiles of 256 x 256, K = 768, one 512-thread workgroup per CU at a
-time) from a debug build (-DPV_ENC_TRACE: PV_NATIVE_LIB=tools/variants/libpvnative_enctrace.so): start, K loop done, end of the hit-list
+time) from a debug build (-DPV_ENC_TRACE, SRC="sae_enc sae_enc_gemm" tools/build_variant.sh enctrace -DPV_ENC_TRACE -- the kernel stamps in sae_enc_gemm.hip, sae_enc.hip hands it the buffer: PV_NATIVE_LIB=tools/variants/libpvnative_enctrace.so): start, K loop done, end of the hit-list
 epilogue on the 100 MHz wall clock.  How long are the three phases of a tile, how long are the gaps between a CU's tiles?"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

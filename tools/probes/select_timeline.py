@@ -1,4 +1,4 @@
-"""Per-workgroup timeline of sae_select_kernel (debug build -DPV_SEL_TRACE: PV_NATIVE_LIB=tools/variants/libpvnative_seltrace.so): start,
+"""Per-workgroup timeline of sae_select_kernel (debug build -DPV_SEL_TRACE, SRC=sae_enc tools/build_variant.sh seltrace -DPV_SEL_TRACE: PV_NATIVE_LIB=tools/variants/libpvnative_seltrace.so): start,
 candidate-pass-done and end stamps of every token's workgroup on the 100 MHz wall clock + its hardware id, one top-k step at the bench
 shape.  Prints the workgroup lifetime distribution, how many are alive over time, and the spread over XCDs / CUs."""
 import os, sys

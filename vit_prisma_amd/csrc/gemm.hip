@@ -20,7 +20,7 @@
 // of k in rising order, so results do not depend on the kernel picked.  gemm_kernel stays on 32x32x16 (it serves only shapes the
 // others cannot take).
 // The K loops of v7 and v8 -- slot geometry, swizzles, step bodies, drivers -- and the XCD-aware tile order live in kloop.hpp,
-// shared with the SAE filter GEMM (sae_enc.hip); the kernels keep their LDS objects, descriptors, piece sources and epilogues.
+// shared with the SAE filter GEMM (sae_enc_gemm.hip); the kernels keep their LDS objects, descriptors, piece sources and epilogues.
 #include <atomic>
 
 #include "gemm_impl.hpp"

@@ -4,7 +4,7 @@
 //                    rows in LDS (ResidParkSrc, -DPV_GEMM_RESID_PARK)
 //   gemm_kernel_v8   v7's full-line form made persistent: a workgroup walks its tiles, their K slabs one stream
 // The K loops -- slot geometry, swizzles, step bodies, drivers -- and the XCD-aware tile order live in kloop.hpp, shared with the SAE
-// filter GEMM (sae_enc.hip); the kernels here keep their LDS objects, descriptors, piece sources and epilogues.
+// filter GEMM (sae_enc_gemm.hip); the kernels here keep their LDS objects, descriptors, piece sources and epilogues.
 // Compiled as part of gemm.hip, which includes it once, beside gemm_v4.hpp (whose head says why the two share a translation unit).
 #pragma once
 #include "gemm_epi.hpp"

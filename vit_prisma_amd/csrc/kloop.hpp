@@ -1,5 +1,5 @@
 // The main loop of the one-workgroup-per-CU MFMA kernels (gfx950): gemm_kernel_v7 / gemm_kernel_v8 (gemm.hip, bf16) and
-// sae_enc_gemm_kernel (sae_enc.hip, fp16).  One 512-thread workgroup (8 waves as 2 (M) x 4 (N)) multiplies a (64*MB) x 256 tile;
+// sae_enc_gemm_kernel (sae_enc_gemm.hip, fp16).  One 512-thread workgroup (8 waves as 2 (M) x 4 (N)) multiplies a (64*MB) x 256 tile;
 // a wave owns (32*MB) x 64 outputs = MB x 2 accumulators of f32x16, multiplied on v_mfma_f32_16x16x32_bf16 (bf16: 2*MB x 4 blocks,
 // four to an accumulator) or v_mfma_f32_32x32x16_f16 (fp16): the shape belongs to the operand tag, see Shape below.  The operands are DMA'd straight into LDS
 // (buffer_load ... lds) in PIECES of 1 KiB = one wave-instruction; wave w moves pieces w, w + 8, ... of a slab's A part and of its

@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include "sae_bwd.hpp"
+#include "sae_enc.hpp"
 
 namespace {
 
@@ -172,7 +173,7 @@ __device__ __forceinline__ void sae_prep_body(int bid, const float* __restrict__
         const float xh = use_ln == 1 ? (xr[i] - mu) / (sd + eps) : (use_ln == 2 ? xr[i] * coeff : xr[i]);
         const float si = i < d_true ? xh - b_dec[i] : 0.f;
         sae_in[(int64_t)n * d + i] = si;
-        if (x16) x16[(int64_t)n * d + i] = (_Float16)si;       // operand of the filter GEMM (sae_enc.hip)
+        if (x16) x16[(int64_t)n * d + i] = (_Float16)si;       // operand of the filter GEMM (sae_enc_gemm.hip)
         s2 += si * si;
         amax = fmaxf(amax, fabsf(si));
     }
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(256) void sae_prep_kernel(const float* __restrict__
 // sums of x (the batch mean's first stage; nblk = 0 when the caller supplied the mean), the other nb_prep = prep without the loss
 // normaliser.  The
 // weight bound max_j ||W_enc[:, j]||^2 of the filter's error band + the zeroing of the per-feature pair counters and the fallback
-// count (sae_wmax_kernel of sae_enc.hip on 256 threads; a maximum does not care about the order)
+// count (enc_wmax_body, sae_enc.hpp: what sae_wmax_kernel of sae_enc.hip runs where there is no fused pre-pass)
 __global__ __launch_bounds__(256) void sae_prep_roles_kernel(const float* __restrict__ x, const float* __restrict__ b_dec,
                                                              float* __restrict__ sae_in, _Float16* __restrict__ x16,
                                                              float* __restrict__ xnorm_out, float* __restrict__ mu_out,
@@ -213,32 +214,7 @@ __global__ __launch_bounds__(256) void sae_prep_roles_kernel(const float* __rest
     } else if (b > 0) {
         colsum_partial_body(b - 1, x, colpart, n_tok, d);
     } else {
-        __shared__ float red[4];
-        // (one workgroup for d_sae values and the launch's long pole: 16-byte accesses, all of a thread's loads in flight at once;
-        // d_sae % 4 == 0 is a plan requirement)
-        const int n4 = d_sae >> 2;
-        if (feat_cnt)
-            for (int j = threadIdx.x; j < n4; j += 256) reinterpret_cast<uint4*>(feat_cnt)[j] = make_uint4(0u, 0u, 0u, 0u);
-        float m = 0.f;
-        constexpr int WM_FL = 12;                                  // (the bench shape: two round trips to memory; 24 in flight cost the launch its occupancy)
-        for (int j0 = threadIdx.x; j0 < n4; j0 += WM_FL * 256) {
-            float4 c[WM_FL];
-#pragma unroll
-            for (int u = 0; u < WM_FL; ++u) c[u] = j0 + u * 256 < n4 ? reinterpret_cast<const float4*>(colsq)[j0 + u * 256] : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int u = 0; u < WM_FL; ++u) {
-                const float e[4] = {c[u].x, c[u].y, c[u].z, c[u].w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) m = (e[i] == e[i]) ? fmaxf(m, e[i]) : INFINITY;      // a NaN column norm poisons the bound (-> exact fallback)
-            }
-        }
-        m = wave_max(m);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            *wmax_out = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-            *fb_count = 0u;
-        }
+        enc_wmax_body(colsq, d_sae, wmax_out, fb_count, feat_cnt);
     }
 }
 

@@ -1,5 +1,6 @@
 // Shared definitions of the SAE step (sae.hip: prep / exact top-k / decode / bias gradients, the plan, the k-sparse step; sae_bwd.hip: the
-// sparse backward; sae_enc.hip: the filtered encoder + top-k; sae_apply.hip: clip norm, Adam, renorm, encoder shadows; sae_tp.hip: the
+// sparse backward; sae_enc.hpp, sae_enc_gemm.hip, sae_enc.hip, sae_enc_relu.hip: the filtered encoder -- its fp16 filter GEMM, the top-k
+// form, the sparse ReLU / gated form; sae_apply.hip: clip norm, Adam, renorm, encoder shadows; sae_tp.hip: the
 // feature-parallel step; sae_dense.hip, sae_dense_gemm.hip, sae_ghost.hip: the dense ReLU + L1 step, its GEMM, ghost gradients;
 // sae_gated.hip, sae_gated_topk.hip: the gated step on the dense GEMM / in its top-k form).
 #pragma once
@@ -82,6 +83,9 @@ constexpr int PV_TOPK_CAP = 1024;            // candidate list capacity of the s
 __device__ __forceinline__ uint32_t pv_f2ord(float f) {
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float pv_ord2f(uint32_t o) {
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 // LDS of the caller: hist[256], cand_key[PV_TOPK_CAP], cand_idx[PV_TOPK_CAP] (sae_select_kernel lends the arrays of its candidate
 // pass: the same sizes); the scalars are this function's own
@@ -269,7 +273,7 @@ struct ReluWs {
     int max_segs;
 };
 ReluWs relu_carve(const pv_sae_desc& d, int n_tokens, int cap);
-// sae_enc.hip: the positive entries of relu(sae_in W_enc + b_enc) per token (see the definition); raises *mode when a token cannot be held
+// sae_enc_relu.hip: the positive entries of relu(sae_in W_enc + b_enc) per token (see the definition); raises *mode when a token cannot be held
 int sae_encode_relu(const pv_sae_desc& d, const pv_sae_state* st, int N, int cap, int32_t* idx, float* val, uint32_t* tok_cnt,
                     float* l1part, uint32_t* cand_cnt, void* cand, uint32_t* feat_cnt, uint32_t* wpos, uint32_t* mode,
                     const float* prev_scalars, unsigned char* wsb, const SaeWs& ws, hipStream_t stream, float* l0part = nullptr,

@@ -428,7 +428,7 @@ extern "C" int pv_sae_dense_step(pv_sae_plan* plan, pv_sae_state* st, const floa
     return rc ? rc : dense_bias_grads(d, st, x, N, wsb, ws, (hipStream_t)stream_);
 }
 
-// The same step, sparse where the batch allows it ("ReLU is top-k with threshold 0 and a variable k", sae_enc.hip: relu_select_kernel):
+// The same step, sparse where the batch allows it ("ReLU is top-k with threshold 0 and a variable k", sae_enc_relu.hip: relu_select_kernel):
 // ONE product over all features -- the fp16 filter with the threshold -B_n and the exact fp32 re-scoring of its survivors -- gives
 // every token's positive activations as a list of at most sp->cap pairs; decode, CSR, the sparse backward and the bias gradients
 // then run on the k-sparse kernels of sae.hip with k = cap (the L1 term: sum of the kept values; its gradient l1 / N on every kept
