@@ -47,11 +47,12 @@ extern "C" {
  * gemm_persist / gemm_stagger tuning keys; 22: pv_sae_desc.activation / lp_norm,
  * normalize_layer_norm = 2 (constant_norm_rescale), the split-fp16 dense GEMMs and their tuning key dense_fp32, gemm_cus;
  * 24: pv_vit_desc.pooling, PV_ATTN_MAX_TOKENS = 2048 (was 640);
- * 25: the supported attention shapes gain the wide heads, 64 < d_head <= 128 with d_head % 8 == 0 (CLIP ViT-H / g / bigG-14)).
+ * 25: the supported attention shapes gain the wide heads, 64 < d_head <= 128 with d_head % 8 == 0 (CLIP ViT-H / g / bigG-14);
+ * 26: pv_vit_forward_from and pv_vit_forward_seg are gone -- pv_vit_forward_stage takes every segment they took).
  * Purely ADDITIVE exports do not bump it: the text tower (pv_text_desc, pv_text_weights, pv_text_plan_create,
  * pv_text_plan_set_weights, pv_text_forward), pv_attention and the logit lens (pv_logit_lens, pv_logit_lens_workspace_bytes,
- * PV_LENS_MAX_STACK) arrived at 25 and left every existing struct layout, signature, slot value and flag as it was, so a caller written against 25 runs unchanged; the Python binding checks the build id besides. */
-#define PV_ABI_VERSION 25
+ * PV_LENS_MAX_STACK) arrived at 25 and left every existing struct layout, signature, slot value and flag as it was; the Python binding checks the build id besides. */
+#define PV_ABI_VERSION 26
 int pv_abi_version(void);
 /* Hash of the sources this binary was built from (sha256 over the .hip / .hpp files of vit_prisma_amd/csrc and this header, names and
  * contents, sorted; first 32 hex digits): the prebuilt library travels next to the sources, and the Python binding refuses
@@ -190,32 +191,11 @@ int pv_vit_forward(pv_vit_plan* plan, const void* images, int32_t batch, int32_t
                    int32_t run_head, const pv_tap* taps, int32_t n_taps, void* workspace,
                    size_t workspace_bytes, void* out, void* stream);
 
-/* The same forward RESUMED at a block boundary: a Python forward hook on blocks.{L}.hook_resid_post /
- * blocks.{L+1}.hook_resid_pre (SAE substitution, zero-ablation: sae/evals/evals.py:321-392) sees the residual the
- * first call tapped, may return a replacement, and the blocks [first_block, n_blocks) (+ head) continue from it --
- * hooked_root_module.py:176-210 semantics ("split the plan at the hook point -> Python -> resume").
- *   resid_in       [B, n_tokens, d_model] T, the residual stream entering block `first_block`
- *                  (first_block == n_layers: only ln_final + head run)
- * Taps of stages before first_block are ignored. */
-int pv_vit_forward_from(pv_vit_plan* plan, const void* resid_in, int32_t batch, int32_t first_block,
-                        int32_t n_blocks, int32_t run_head, const pv_tap* taps, int32_t n_taps,
-                        void* workspace, size_t workspace_bytes, void* out, void* stream);
-
-/* General form of the two calls above: one SEGMENT of the forward, for hooks that sit in the middle of a block too
- * (blocks.L.hook_attn_out / hook_resid_mid).  Positions are (block, half): half 0 = the block's entry, half 1 = after
- * its attention half (the residual stream is resid_mid there).
- *   images / resid_in   exactly one is non-NULL: start from the pixels (first_block = entry_mid = 0) or resume from a
- *                       residual -- the one entering block first_block, or with entry_mid = 1 its resid_mid
- *   end_block, exit_mid run up to the entry of block end_block, or with exit_mid = 1 also through the attention half of
- *                       block end_block (tap PV_SLOT_RESID_MID there to get the result)
- *   run_head            only with end_block == n_layers and exit_mid == 0 */
-int pv_vit_forward_seg(pv_vit_plan* plan, const void* images, const void* resid_in, int32_t batch,
-                       int32_t first_block, int32_t entry_mid, int32_t end_block, int32_t exit_mid,
-                       int32_t run_head, const pv_tap* taps, int32_t n_taps, void* workspace,
-                       size_t workspace_bytes, void* out, void* stream);
-
-/* The finest form: segments that start / stop at any of a block's ten hookable positions, so that mutating hooks INSIDE the
- * attention half and the MLP keep the native path too (head ablation through attn.hook_z, neuron ablation through
+/* One SEGMENT of the same forward: it starts from the pixels or is RESUMED from a residual stream, and starts / stops at a block
+ * boundary or at any of a block's ten hookable positions.  A Python forward hook (SAE substitution, zero-ablation:
+ * sae/evals/evals.py:321-392) sees what the segment before it tapped, may return a replacement, and the next segment continues from
+ * it -- hooked_root_module.py:176-210 semantics ("split the plan at the hook point -> Python -> resume") -- so that mutating hooks
+ * on the residual stream and INSIDE the attention half and the MLP keep the native path (head ablation through attn.hook_z, neuron ablation through
  * mlp.hook_post, edits of attn.hook_q / hook_k / hook_v, of attn.hook_attn_scores, of attn.hook_pattern, of mlp.hook_pre and of the
  * LayerNorm points ln1 / ln2 .hook_scale / .hook_normalized ("frozen LayerNorm"): prisma_tools/hook_point.py:44-45 -- a hook's
  * return value replaces the activation -- with models/layers/attention.py:135-152, 186-281, mlp.py:65-80 and layer_norm.py:75-93).
@@ -226,11 +206,16 @@ int pv_vit_forward_seg(pv_vit_plan* plan, const void* images, const void* resid_
 #define PV_STAGE_SCORES 3     /* attention scores computed (attn.hook_attn_scores)                                         */
 #define PV_STAGE_PATTERN 4    /* softmax taken (attn.hook_pattern)                                                         */
 #define PV_STAGE_Z 5          /* attention core done (attn.hook_z)                                                        */
-#define PV_STAGE_MID 6        /* after the O-projection + residual add (hook_attn_out, hook_resid_mid) == entry_mid above  */
+#define PV_STAGE_MID 6        /* after the O-projection + residual add (hook_attn_out, hook_resid_mid)                    */
 #define PV_STAGE_LN2 7        /* ln2 taken (ln2.hook_scale, ln2.hook_normalized)                                           */
 #define PV_STAGE_MLP_PRE 8    /* MLP pre-activation computed (mlp.hook_pre)                                                */
 #define PV_STAGE_MLP_POST 9   /* MLP activation computed (mlp.hook_post)                                                  */
-/*   exit_stage   != 0: the segment also runs block end_block up to that position and stops; the caller taps what the hook
+/*   images / resid_in   exactly one is non-NULL: start from the pixels (first_block = entry_stage = 0), or resume from resid_in
+ *                [B, n_tokens, d_model] T: with entry_stage == 0 the residual stream entering block first_block (first_block ==
+ *                n_layers: only ln_final + head run).  Taps of stages before the entry are ignored.
+ *   end_block    run up to the entry of block end_block (first_block <= end_block <= n_layers); run_head only with
+ *                end_block == n_layers and exit_stage == 0
+ *   exit_stage   != 0: the segment also runs block end_block up to that position and stops; the caller taps what the hook
  *                needs (PV_SLOT_LN1_SCALE / LN1_NORM_F32 (bf16 mode; LN1_OUT in fp32 mode), PV_SLOT_Q / K / V, PV_SLOT_SCORES,
  *                PV_SLOT_PATTERN, PV_SLOT_Z, PV_SLOT_RESID_MID, PV_SLOT_LN2_*, PV_SLOT_MLP_PRE, PV_SLOT_MLP_POST; for SCORES / PATTERN also
  *                PV_SLOT_V, which the resumed attention core reads) and -- to resume -- the residual stream the rest of the block

@@ -81,7 +81,7 @@ def _desc(d_head):
 
 def test_plan_creation_accepts_wide_heads_and_states_the_rule_when_it_refuses():
     lib = _native.lib()
-    assert lib.pv_abi_version() == _native.ABI_VERSION == 25
+    assert lib.pv_abi_version() == _native.ABI_VERSION == 26
     plan = C.c_void_p()
     for d_head in (80, 104):
         desc = _desc(d_head)

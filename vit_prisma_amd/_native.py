@@ -11,7 +11,7 @@ from typing import Optional
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PV_NATIVE_LIB") or os.path.join(HERE, "libpvnative.so")     # (override: kernel A/B builds)
-ABI_VERSION = 25
+ABI_VERSION = 26
 ATTN_MAX_TOKENS = 2048            # PV_ATTN_MAX_TOKENS of include/pv_native.h (held equal by tests/test_dino_cpu.py)
 PV_POOL_CLS, PV_POOL_MEAN, PV_POOL_CLS_MEAN = 0, 1, 2
 
@@ -121,7 +121,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "pv_abi_version", "pv_build_id", "pv_last_error",
     "pv_vit_plan_create", "pv_vit_plan_destroy", "pv_vit_shadow_bytes", "pv_vit_plan_set_weights",
-    "pv_vit_workspace_bytes", "pv_vit_forward", "pv_vit_forward_from", "pv_vit_forward_seg", "pv_vit_forward_stage",
+    "pv_vit_workspace_bytes", "pv_vit_forward", "pv_vit_forward_stage",
     "pv_text_plan_create", "pv_text_plan_set_weights", "pv_text_forward", "pv_attention", "pv_gemm_bias", "pv_gemm_epilogue", "pv_transpose_batched",
     "pv_prof_enable", "pv_prof_reset", "pv_prof_read", "pv_prof_read_tag",
     "pv_sae_plan_create", "pv_sae_plan_destroy", "pv_sae_workspace_bytes", "pv_sae_renorm_decoder",
@@ -171,8 +171,6 @@ def lib() -> C.CDLL:
     L.pv_vit_workspace_bytes.argtypes = [vp, i32]
     L.pv_vit_workspace_bytes.restype = sz
     L.pv_vit_forward.argtypes = [vp, vp, i32, i32, i32, C.POINTER(Tap), i32, vp, sz, vp, vp]
-    L.pv_vit_forward_from.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(Tap), i32, vp, sz, vp, vp]
-    L.pv_vit_forward_seg.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Tap), i32, vp, sz, vp, vp]
     L.pv_vit_forward_stage.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Tap), i32, vp, sz, vp, vp]
     L.pv_text_plan_create.argtypes = [C.POINTER(TextDesc), C.POINTER(vp)]
     L.pv_text_plan_set_weights.argtypes = [vp, C.POINTER(TextWeights), vp, sz, vp]

@@ -260,390 +260,392 @@ extern "C" size_t pv_vit_workspace_bytes(const pv_vit_plan* p, int32_t batch) {
     return carve(p, batch).total;
 }
 
+// ---- the tapped forward ---------------------------------------------------------------------
 namespace {
-// entry_stage / exit_stage: PV_STAGE_* (positions inside a block: entry, ln1, q/k/v ready, scores, pattern, z ready, resid_mid, ln2, mlp pre, mlp post ready)
-int vit_forward_impl(pv_vit_plan* p, const void* images, const int64_t* tokens, const void* resid_in, const void* const* act_in, int32_t B,
-                     int32_t first_block, int32_t entry_stage, int32_t n_blocks, int32_t exit_stage, int32_t run_head,
-                     const pv_tap* taps, int32_t n_taps, void* workspace, size_t workspace_bytes, void* out, void* stream_);
-}  // namespace
-
-extern "C" int pv_vit_forward(pv_vit_plan* p, const void* images, int32_t B, int32_t n_blocks,
-                              int32_t run_head, const pv_tap* taps, int32_t n_taps, void* workspace,
-                              size_t workspace_bytes, void* out, void* stream_) {
-    PV_REQUIRE(images, "null argument");
-    return vit_forward_impl(p, images, nullptr, nullptr, nullptr, B, 0, 0, n_blocks, 0, run_head, taps, n_taps, workspace, workspace_bytes, out, stream_);
+// One call runs one SEGMENT of the forward: from the model input, or from a residual stream resumed at position
+// (first_block, entry_stage), to position (end_block, exit_stage), + the head.  Stages are PV_STAGE_* (positions inside a block: entry,
+// ln1, q/k/v ready, scores, pattern, z ready, resid_mid, ln2, mlp pre, mlp post ready).  Every entry point fills one of these.
+struct Segment {
+    const void* images;        // vision plan: exactly one of images / resid_in
+    const int64_t* tokens;     // text plan (pv_text_forward alone passes them)
+    const void* resid_in;      // the residual stream the rest of block first_block adds to: resid_pre up to PV_STAGE_Z, resid_mid behind
+    const void* act_in[3];     // the (hook-edited) activations of entry_stage: ln normalized fp32 | q, k, v | scores, v | pattern, v | z | mlp pre | mlp post
+    int32_t B, first_block, entry_stage, end_block, exit_stage, run_head, n_taps;
+    const pv_tap* taps;
+    void *workspace, *out;
+    size_t workspace_bytes;
+    hipStream_t stream;
+};
+Segment segment_io(int32_t B, int32_t run_head, const pv_tap* taps, int32_t n_taps, void* workspace, size_t workspace_bytes, void* out, void* stream) {
+    Segment s = {};
+    s.B = B; s.run_head = run_head; s.taps = taps; s.n_taps = n_taps;
+    s.workspace = workspace; s.workspace_bytes = workspace_bytes; s.out = out; s.stream = (hipStream_t)stream;
+    return s;
 }
 
-extern "C" int pv_vit_forward_seg(pv_vit_plan* p, const void* images, const void* resid_in, int32_t B, int32_t first_block,
-                                  int32_t entry_mid, int32_t end_block, int32_t exit_mid, int32_t run_head, const pv_tap* taps,
-                                  int32_t n_taps, void* workspace, size_t workspace_bytes, void* out, void* stream_) {
-    PV_REQUIRE(p && ((images != nullptr) != (resid_in != nullptr)), "exactly one of images / resid_in");
-    PV_REQUIRE(!resid_in || pv_aligned16(resid_in), "resid_in must be 16-byte aligned");
-    PV_REQUIRE(images ? (first_block == 0 && !entry_mid) : (first_block >= 0 && first_block <= p->d.n_layers), "segment start");
-    PV_REQUIRE(first_block <= end_block && end_block <= p->d.n_layers, "segment end");
-    PV_REQUIRE(!entry_mid || first_block < p->d.n_layers, "entry_mid needs a block to resume");
-    PV_REQUIRE(!exit_mid || (end_block < p->d.n_layers && !run_head), "exit_mid stops inside block end_block");
-    PV_REQUIRE(!(entry_mid && first_block == end_block && !exit_mid), "a mid-block entry must finish its block");
-    return vit_forward_impl(p, images, nullptr, resid_in, nullptr, B, first_block, entry_mid ? PV_STAGE_MID : 0, end_block,
-                            exit_mid ? PV_STAGE_MID : 0, run_head, taps, n_taps, workspace, workspace_bytes, out, stream_);
-}
-
-extern "C" int pv_vit_forward_stage(pv_vit_plan* p, const void* images, const void* resid_in, const void* act_in0, const void* act_in1,
-                                    const void* act_in2, int32_t B, int32_t first_block, int32_t entry_stage, int32_t end_block,
-                                    int32_t exit_stage, int32_t run_head, const pv_tap* taps, int32_t n_taps, void* workspace,
-                                    size_t workspace_bytes, void* out, void* stream_) {
-    PV_REQUIRE(p && ((images != nullptr) != (resid_in != nullptr)), "exactly one of images / resid_in");
-    PV_REQUIRE(!resid_in || pv_aligned16(resid_in), "resid_in must be 16-byte aligned");
+// Every rule of a call, before any launch; carves the workspace on the way.  (split_plan.py's EXIT table states the act_in rows.)
+int check_segment(const pv_vit_plan* p, const Segment& s, Workspace& ws) {
+    PV_REQUIRE(p && s.workspace, "null argument");
+    const int32_t n_layers = p->d.n_layers, first_block = s.first_block, end_block = s.end_block, entry_stage = s.entry_stage,
+                  exit_stage = s.exit_stage, run_head = s.run_head;
+    const void* const* act_in = s.act_in;
+    PV_REQUIRE(s.tokens || ((s.images != nullptr) != (s.resid_in != nullptr)), "exactly one of images / resid_in");
+    PV_REQUIRE(!s.resid_in || pv_aligned16(s.resid_in), "resid_in must be 16-byte aligned");
     PV_REQUIRE(entry_stage >= 0 && entry_stage <= PV_STAGE_MLP_POST && exit_stage >= 0 && exit_stage <= PV_STAGE_MLP_POST, "stage");
-    PV_REQUIRE(images ? (first_block == 0 && !entry_stage) : (first_block >= 0 && first_block <= p->d.n_layers), "segment start");
-    PV_REQUIRE(first_block <= end_block && end_block <= p->d.n_layers, "segment end");
-    PV_REQUIRE(!entry_stage || first_block < p->d.n_layers, "a mid-block entry needs a block to resume");
-    PV_REQUIRE(!exit_stage || (end_block < p->d.n_layers && !run_head), "a mid-block exit stops inside block end_block");
+    PV_REQUIRE(s.resid_in ? (first_block >= 0 && first_block <= n_layers) : (first_block == 0 && !entry_stage), "segment start");
+    PV_REQUIRE(first_block <= end_block && end_block <= n_layers, "segment end (n_blocks out of range)");
+    PV_REQUIRE(!entry_stage || first_block < n_layers, "a mid-block entry needs a block to resume");
+    PV_REQUIRE(!exit_stage || (end_block < n_layers && !run_head), "a mid-block exit stops inside block end_block");
     PV_REQUIRE(first_block < end_block || entry_stage < exit_stage || (first_block == end_block && !exit_stage && !entry_stage),
                "empty or backward segment");
-    if (entry_stage == PV_STAGE_QKV) PV_REQUIRE(act_in0 && act_in1 && act_in2, "entry at PV_STAGE_QKV needs q, k, v");
+    if (entry_stage == PV_STAGE_QKV) PV_REQUIRE(act_in[0] && act_in[1] && act_in[2], "entry at PV_STAGE_QKV needs q, k, v");
     if (entry_stage == PV_STAGE_Z || entry_stage == PV_STAGE_MLP_POST || entry_stage == PV_STAGE_LN1 || entry_stage == PV_STAGE_LN2 ||
         entry_stage == PV_STAGE_MLP_PRE)
-        PV_REQUIRE(act_in0, "entry at PV_STAGE_LN1 / Z / LN2 / MLP_PRE / MLP_POST needs the activation");
-    if (entry_stage == PV_STAGE_SCORES || entry_stage == PV_STAGE_PATTERN) PV_REQUIRE(act_in0 && act_in1, "entry at PV_STAGE_SCORES / PV_STAGE_PATTERN needs the activation and v");
-    const void* act[3] = {act_in0, act_in1, act_in2};
-    for (int i = 0; i < 3; ++i) PV_REQUIRE(!act[i] || pv_aligned16(act[i]), "activation inputs must be 16-byte aligned");
-    return vit_forward_impl(p, images, nullptr, resid_in, act, B, first_block, entry_stage, end_block, exit_stage, run_head, taps, n_taps,
-                            workspace, workspace_bytes, out, stream_);
-}
-
-extern "C" int pv_vit_forward_from(pv_vit_plan* p, const void* resid_in, int32_t B, int32_t first_block, int32_t n_blocks,
-                                   int32_t run_head, const pv_tap* taps, int32_t n_taps, void* workspace,
-                                   size_t workspace_bytes, void* out, void* stream_) {
-    PV_REQUIRE(resid_in && pv_aligned16(resid_in), "resid_in must be a 16-byte aligned device pointer");
-    PV_REQUIRE(p && first_block >= 0 && first_block <= p->d.n_layers && first_block <= n_blocks, "first_block out of range");
-    return vit_forward_impl(p, nullptr, nullptr, resid_in, nullptr, B, first_block, 0, n_blocks, 0, run_head, taps, n_taps, workspace, workspace_bytes, out, stream_);
-}
-
-namespace {
-int vit_forward_impl(pv_vit_plan* p, const void* images, const int64_t* tokens, const void* resid_in, const void* const* act_in, int32_t B,
-                     int32_t first_block, int32_t entry_stage, int32_t n_blocks, int32_t exit_stage, int32_t run_head,
-                     const pv_tap* taps, int32_t n_taps, void* workspace, size_t workspace_bytes, void* out, void* stream_) {
-    PV_REQUIRE(p && (images || tokens || resid_in) && workspace, "null argument");
-    // tokens: only pv_text_forward passes them, and only for a text plan -- refused here, before any launch
-    PV_REQUIRE(p->is_text == (tokens != nullptr), "a text plan runs through pv_text_forward, a vision plan through pv_vit_forward*");
+        PV_REQUIRE(act_in[0], "entry at PV_STAGE_LN1 / Z / LN2 / MLP_PRE / MLP_POST needs the activation");
+    if (entry_stage == PV_STAGE_SCORES || entry_stage == PV_STAGE_PATTERN)
+        PV_REQUIRE(act_in[0] && act_in[1], "entry at PV_STAGE_SCORES / PV_STAGE_PATTERN needs the activation and v");
+    for (int i = 0; i < 3; ++i) PV_REQUIRE(!act_in[i] || pv_aligned16(act_in[i]), "activation inputs must be 16-byte aligned");
+    PV_REQUIRE(!s.tokens || p->is_text, "pv_text_forward needs a plan of pv_text_plan_create (a vision plan runs through pv_vit_forward*)");
+    PV_REQUIRE(s.tokens || !p->is_text, "a text plan runs through pv_text_forward, a vision plan through pv_vit_forward*");
     PV_REQUIRE(p->weights_set, "pv_vit_plan_set_weights has not been called");
-    PV_REQUIRE(B > 0, "batch must be positive");
-    const pv_vit_desc& d = p->d;
-    PV_REQUIRE(n_blocks >= 0 && n_blocks <= d.n_layers, "n_blocks out of range");
-    PV_REQUIRE(!run_head || n_blocks == d.n_layers, "run_head requires all blocks");
-    PV_REQUIRE(!run_head || out, "run_head requires an output buffer");
-    PV_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    PV_REQUIRE(!images || pv_aligned16(images), "images must be 16-byte aligned");
-    const Workspace ws = carve(p, B);
-    PV_REQUIRE(workspace_bytes >= ws.total, "workspace too small");
-    hipStream_t stream = (hipStream_t)stream_;
-    unsigned char* wsb = (unsigned char*)workspace;
-    const int dt = d.dtype, T = p->T, dm = d.d_model, HD = p->HD, dmlp = d.d_mlp;
-    const int M = B * T;
-    const bool bf16 = dt == PV_DTYPE_BF16;
+    PV_REQUIRE(s.B > 0, "batch must be positive");
+    PV_REQUIRE(!run_head || end_block == n_layers, "run_head requires all blocks");
+    PV_REQUIRE(!run_head || s.out, "run_head requires an output buffer");
+    PV_REQUIRE(((uintptr_t)s.workspace & 255) == 0, "workspace must be 256-byte aligned");
+    PV_REQUIRE(!s.images || pv_aligned16(s.images), "images must be 16-byte aligned");
+    ws = carve(p, s.B);
+    PV_REQUIRE(s.workspace_bytes >= ws.total, "workspace too small");
+    return PV_OK;
+}
 
-    // tap table
-    std::vector<void*> tap((size_t)PV_SLOT__COUNT * (size_t)(d.n_layers + 1), nullptr);
-    auto tap_at = [&](int slot, int layer) -> void*& { return tap[(size_t)layer * PV_SLOT__COUNT + slot]; };
-    for (int i = 0; i < n_taps; ++i) {
-        const pv_tap& t = taps[i];
-        PV_REQUIRE(t.slot >= 0 && t.slot < PV_SLOT__COUNT && t.dst, "bad tap slot");
-        const int layer = t.slot >= PV_SLOT_LN1_SCALE ? t.layer : 0;
-        PV_REQUIRE(layer >= 0 && layer < d.n_layers + 1, "bad tap layer");
-        PV_REQUIRE(pv_aligned16(t.dst), "tap destinations must be 16-byte aligned");
-        if (!bf16) {
-            PV_REQUIRE(t.slot != PV_SLOT_LNPRE_NORM_F32 && t.slot != PV_SLOT_LNF_NORM_F32 &&
-                           t.slot != PV_SLOT_LN1_NORM_F32 && t.slot != PV_SLOT_LN2_NORM_F32,
+// What the steps of one call share.
+struct Fwd {
+    const pv_vit_plan* p;
+    const pv_vit_desc& d;
+    const Segment& s;
+    const void* const* act_in;
+    const int dt, B, T, M;
+    const bool bf16;
+    const hipStream_t stream;
+    unsigned char* const wsb;
+    const Workspace ws;
+    std::vector<void*> tap;     // [layer][slot]: where a tapped buffer goes, nullptr = not tapped
+    bool resid_in_a = true;     // which workspace residual buffer may hold the residual stream
+    Fwd(const pv_vit_plan* p, const Segment& s, const Workspace& ws)
+        : p(p), d(p->d), s(s), act_in(s.act_in), dt(p->d.dtype), B(s.B), T(p->T), M(s.B * p->T), bf16(p->d.dtype == PV_DTYPE_BF16),
+          stream(s.stream), wsb((unsigned char*)s.workspace), ws(ws), tap((size_t)PV_SLOT__COUNT * (size_t)(p->d.n_layers + 1), nullptr) {}
+    void*& tap_at(int slot, int layer) { return tap[(size_t)layer * PV_SLOT__COUNT + slot]; }
+    // the tap's destination when the slot is tapped, else its workspace buffer
+    void* pick(int slot, int layer, size_t ws_off) { return tap_at(slot, layer) ? tap_at(slot, layer) : (void*)(wsb + ws_off); }
+    int set_taps(const pv_tap* taps, int n_taps) {
+        for (int i = 0; i < n_taps; ++i) {
+            const pv_tap& t = taps[i];
+            PV_REQUIRE(t.slot >= 0 && t.slot < PV_SLOT__COUNT && t.dst, "bad tap slot");
+            const int layer = t.slot >= PV_SLOT_LN1_SCALE ? t.layer : 0;
+            PV_REQUIRE(layer >= 0 && layer < d.n_layers + 1, "bad tap layer");
+            PV_REQUIRE(pv_aligned16(t.dst), "tap destinations must be 16-byte aligned");
+            PV_REQUIRE(bf16 || (t.slot != PV_SLOT_LNPRE_NORM_F32 && t.slot != PV_SLOT_LNF_NORM_F32 &&
+                                t.slot != PV_SLOT_LN1_NORM_F32 && t.slot != PV_SLOT_LN2_NORM_F32),
                        "*_NORM_F32 slots exist only in bf16 mode");
-        }
-        if (p->is_text) {
-            PV_REQUIRE(t.slot != PV_SLOT_LNPRE_SCALE && t.slot != PV_SLOT_LNPRE_NORM_F32 && t.slot != PV_SLOT_LNPRE_OUT,
+            PV_REQUIRE(!p->is_text || (t.slot != PV_SLOT_LNPRE_SCALE && t.slot != PV_SLOT_LNPRE_NORM_F32 && t.slot != PV_SLOT_LNPRE_OUT),
                        "a text plan has no PV_SLOT_LNPRE_* slots: ln_pre never runs (base_text_transformer.py:139-146)");
+            tap_at(t.slot, layer) = t.dst;
         }
-        tap_at(t.slot, layer) = t.dst;
+        return PV_OK;
     }
-    auto pick = [&](int slot, int layer, size_t ws_off) -> void* {
-        void* t = tap_at(slot, layer);
-        return t ? t : (void*)(wsb + ws_off);
-    };
+};
+
+// what the six linear layers' GEMMs share; the call sites set the epilogue's operands (and the patch gather's A mode)
+GemmParams linear(const void* A, int64_t lda, const void* Bt, int64_t ldb, int M, int N, int K, int epi) {
+    GemmParams g = {};
+    g.A = A; g.lda = lda; g.a_mode = PV_A_PLAIN; g.Bt = Bt; g.ldb = ldb; g.M = M; g.N = N; g.K = K; g.epi = epi;
+    return g;
+}
+
+// ---- patch embedding: stride-p conv as an im2col-free GEMM (patch_embedding.py:26-32), then cls + pos (+ ln_pre) (base_vit.py:171-185)
+int embed_vision(Fwd& F, void*& resid) {
+    const pv_vit_plan* p = F.p;
+    const pv_vit_desc& d = F.d;
+    const void* images = F.s.images;
+    const int dm = d.d_model, K = d.n_channels * d.patch_size * d.patch_size;
+    void* embed = F.pick(PV_SLOT_EMBED, 0, F.ws.embed);
+    GemmParams g;
     int rc;
-
-    void* resid;
-    if (resid_in) {
-        // resumed forward (pv_vit_forward_from): the caller hands in the residual stream entering `first_block`
-        // (the value a Python hook at a block boundary returned); the embedding stages are skipped
-        resid = const_cast<void*>(resid_in);
-    } else if (p->is_text) {
-        // ---- token + position embedding (base_text_transformer.py:125-143): hook_embed is the gather itself, hook_full_embed the
-        // residual stream entering block 0
-        resid = pick(PV_SLOT_FULL_EMBED, 0, ws.resid_a);
-        if ((rc = pv_launch_token_embed(dt, tokens, p->token_embed, p->pos_embed, tap_at(PV_SLOT_EMBED, 0), resid, B, T, dm, p->vocab, stream))) return rc;
+    if (p->patch_prepack && ((uintptr_t)images & 3) == 0) {
+        void* rows = F.wsb + F.ws.patches;
+        if ((rc = pv_launch_patch_pack_bf16(images, rows, F.B, d.n_channels, d.image_size, d.patch_size, p->G, p->Kp, F.stream))) return rc;
+        g = linear(rows, p->Kp, p->conv_wp, p->Kp, F.B * p->P, dm, p->Kp, PV_EPI_BIAS);
     } else {
-    // ---- patch embedding: stride-p conv as an im2col-free GEMM (patch_embedding.py:26-32)
-    void* embed = pick(PV_SLOT_EMBED, 0, ws.embed);
-    {
-        GemmParams g = {};
-        if (p->patch_prepack && ((uintptr_t)images & 3) == 0) {
-            void* rows = wsb + ws.patches;
-            if ((rc = pv_launch_patch_pack_bf16(images, rows, B, d.n_channels, d.image_size, d.patch_size, p->G, p->Kp, stream))) return rc;
-            g.A = rows; g.lda = p->Kp; g.a_mode = PV_A_PLAIN; g.Bt = p->conv_wp; g.ldb = p->Kp; g.K = p->Kp;
-        } else {
-            g.A = images; g.a_mode = PV_A_PATCH; g.pC = d.n_channels; g.pP = d.patch_size; g.pS = d.image_size; g.pG = p->G;
-            g.Bt = p->w.conv_w; g.ldb = (int64_t)d.n_channels * d.patch_size * d.patch_size;
-            g.K = d.n_channels * d.patch_size * d.patch_size;
-        }
-        g.M = B * p->P; g.N = dm;
-        g.epi = PV_EPI_BIAS; g.bias0 = p->w.conv_b; g.out0 = embed; g.ldo = dm;
-        if ((rc = pv_launch_gemm(dt, g, stream))) return rc;
+        g = linear(images, 0, p->w.conv_w, K, F.B * p->P, dm, K, PV_EPI_BIAS);
+        g.a_mode = PV_A_PATCH; g.pC = d.n_channels; g.pP = d.patch_size; g.pS = d.image_size; g.pG = p->G;
     }
-    // ---- cls + pos (+ ln_pre) (base_vit.py:171-185)
-    {
-        LnParams L = {};
-        L.x = embed; L.rows = M; L.d = dm; L.eps = d.eps; L.embed = 1; L.T = T; L.use_cls = d.use_cls_token ? 1 : 0;
-        L.cls = p->w.cls_token; L.pos = p->w.W_pos;
-        if (d.layer_norm_pre) {
-            L.do_ln = 1; L.w = p->w.ln_pre_w; L.b = p->w.ln_pre_b;
-            L.full_out = tap_at(PV_SLOT_FULL_EMBED, 0);
-            L.scale_out = (float*)tap_at(PV_SLOT_LNPRE_SCALE, 0);
-            L.norm_f32_out = (float*)tap_at(PV_SLOT_LNPRE_NORM_F32, 0);
-            resid = pick(PV_SLOT_LNPRE_OUT, 0, ws.resid_a);
-            L.out = resid;
-        } else {
-            L.do_ln = 0;
-            resid = pick(PV_SLOT_FULL_EMBED, 0, ws.resid_a);
-            L.full_out = resid;
-        }
-        if ((rc = pv_launch_ln(dt, L, stream))) return rc;
+    g.bias0 = p->w.conv_b; g.out0 = embed; g.ldo = dm;
+    if ((rc = pv_launch_gemm(F.dt, g, F.stream))) return rc;
+    LnParams L = {};
+    L.x = embed; L.rows = F.M; L.d = dm; L.eps = d.eps; L.embed = 1; L.T = F.T; L.use_cls = d.use_cls_token ? 1 : 0;
+    L.cls = p->w.cls_token; L.pos = p->w.W_pos;
+    if (d.layer_norm_pre) {
+        L.do_ln = 1; L.w = p->w.ln_pre_w; L.b = p->w.ln_pre_b;
+        L.full_out = F.tap_at(PV_SLOT_FULL_EMBED, 0);
+        L.scale_out = (float*)F.tap_at(PV_SLOT_LNPRE_SCALE, 0);
+        L.norm_f32_out = (float*)F.tap_at(PV_SLOT_LNPRE_NORM_F32, 0);
+        resid = F.pick(PV_SLOT_LNPRE_OUT, 0, F.ws.resid_a);
+        L.out = resid;
+    } else {
+        L.do_ln = 0;
+        resid = F.pick(PV_SLOT_FULL_EMBED, 0, F.ws.resid_a);
+        L.full_out = resid;
     }
-    }
-    bool resid_in_a = true;   // which workspace residual buffer may hold `resid`
+    return pv_launch_ln(F.dt, L, F.stream);
+}
 
-    // blocks [first_block, n_blocks) in full; with exit_stage also block n_blocks up to that stage (the caller taps what it
-    // needs there); with entry_stage the first block resumes behind that stage: `resid` is then the residual stream the
-    // rest of the block adds to (resid_pre for PV_STAGE_QKV / PV_STAGE_Z, resid_mid for PV_STAGE_MID / PV_STAGE_MLP_POST) and
-    // act_in holds the (hook-edited) activations of the stage: q, k, v | z | mlp post
-    const int last_block = exit_stage ? n_blocks + 1 : n_blocks;
-    for (int l = first_block; l < last_block; ++l) {
-        const pv_vit_layer_weights& W = p->lw[l];
-        const LayerShadow& S = p->sh[l];
-        const int es = l == first_block ? entry_stage : 0;
-        const int xs = (exit_stage && l == n_blocks) ? exit_stage : 99;
-        void* resid_pre = resid;
-        void* resid_mid = nullptr;
-        void *q = nullptr, *k = nullptr, *v = nullptr, *z = nullptr;
-        if (es >= PV_STAGE_MID) {
-            resid_mid = resid;
-        } else {
-        void* ln1 = nullptr;
-        if (es < PV_STAGE_LN1) {
-        // ln1 (transformer_block.py:106-109 ; layer_norm.py:75-93)
-        ln1 = pick(PV_SLOT_LN1_OUT, l, ws.ln_out);
-        {
-            LnParams L = {};
-            L.x = resid_pre; L.ldx = dm; L.rows = M; L.d = dm; L.eps = d.eps; L.do_ln = 1;
-            L.w = W.ln1_w; L.b = W.ln1_b;
-            L.scale_out = (float*)tap_at(PV_SLOT_LN1_SCALE, l);
-            L.norm_f32_out = (float*)tap_at(PV_SLOT_LN1_NORM_F32, l);
-            L.out = ln1;
-            if ((rc = pv_launch_ln(dt, L, stream))) return rc;
-        }
-        } else if (es == PV_STAGE_LN1) {
-            // behind a hooked ln1.hook_scale / hook_normalized: the (edited) fp32 normalized tensor, rounded to the storage
-            // dtype like the module's own last step (layer_norm.py:93)
-            if (bf16) {
-                ln1 = wsb + ws.ln_out;
-                if ((rc = pv_launch_cast_from_f32(dt, (const float*)act_in[0], ln1, (int64_t)M * dm, stream))) return rc;
-            } else {
-                ln1 = const_cast<void*>(act_in[0]);
-            }
-        }
-        if (xs == PV_STAGE_LN1) break;
-        if (es < PV_STAGE_QKV) {
-        // q, k, v (attention.py:186-244) as one GEMM against the packed [3*H*dh][d] shadow
-        q = pick(PV_SLOT_Q, l, ws.q);
-        k = pick(PV_SLOT_K, l, ws.k);
-        v = pick(PV_SLOT_V, l, ws.v);
-        {
-            GemmParams g = {};
-            g.A = ln1; g.lda = dm; g.a_mode = PV_A_PLAIN; g.Bt = S.Wqkv; g.ldb = dm;
-            g.M = M; g.N = 3 * HD; g.K = dm; g.epi = PV_EPI_QKV; g.nsplit = HD;
-            g.bias0 = W.b_Q; g.bias1 = W.b_K; g.bias2 = W.b_V; g.out0 = q; g.out1 = k; g.out2 = v; g.ldo = HD;
-            if ((rc = pv_launch_gemm(dt, g, stream))) return rc;
-        }
-        } else if (es == PV_STAGE_QKV) {
-            q = const_cast<void*>(act_in[0]); k = const_cast<void*>(act_in[1]); v = const_cast<void*>(act_in[2]);
-        }
-        if (xs == PV_STAGE_QKV) break;
-        if (es < PV_STAGE_SCORES) {
-        // scores / pattern / z (attention.py:135-152, 246-281)
-        z = pick(PV_SLOT_Z, l, ws.z);
-        {
-            AttnParams a = {};
-            a.q = q; a.k = k; a.v = v; a.z = z;
-            a.scores = tap_at(PV_SLOT_SCORES, l); a.pattern = tap_at(PV_SLOT_PATTERN, l);
-            a.B = B; a.T = T; a.H = d.n_heads; a.dh = d.d_head; a.attn_scale = d.attn_scale; a.causal = p->causal;
-            if ((rc = pv_launch_attention(dt, a, stream))) return rc;
-        }
-        } else if (es == PV_STAGE_SCORES || es == PV_STAGE_PATTERN) {
-            // behind a hooked hook_attn_scores / hook_pattern: the rest of the core from the edited tensor and v
-            z = pick(PV_SLOT_Z, l, ws.z);
-            AttnParams a = {};
-            a.v = act_in[1]; a.z = z;
-            if (es == PV_STAGE_SCORES) { a.scores = const_cast<void*>(act_in[0]); a.pattern = tap_at(PV_SLOT_PATTERN, l); }
-            else a.pattern = const_cast<void*>(act_in[0]);
-            a.B = B; a.T = T; a.H = d.n_heads; a.dh = d.d_head; a.attn_scale = d.attn_scale;
-            if ((rc = pv_launch_attention_resume(dt, a, es == PV_STAGE_SCORES ? 1 : 0, stream))) return rc;
-        } else {
-            z = const_cast<void*>(act_in[0]);
-        }
-        if (xs == PV_STAGE_SCORES || xs == PV_STAGE_PATTERN || xs == PV_STAGE_Z) break;
-        // attn_out = z W_O + b_O ; resid_mid = resid_pre + attn_out (attention.py:155-167 ; block :117-124)
-        resid_mid = pick(PV_SLOT_RESID_MID, l, ws.resid_mid);
-        {
-            GemmParams g = {};
-            g.A = z; g.lda = HD; g.a_mode = PV_A_PLAIN; g.Bt = S.WoT; g.ldb = HD;
-            g.M = M; g.N = dm; g.K = HD; g.epi = PV_EPI_RESID; g.bias0 = W.b_O;
-            g.out0 = tap_at(PV_SLOT_ATTN_OUT, l); g.out1 = resid_mid; g.ldo = dm; g.resid = resid_pre; g.ldr = dm;
-            if ((rc = pv_launch_gemm(dt, g, stream))) return rc;
-        }
-        }
-        if (xs == PV_STAGE_MID) {
-            resid = resid_mid;
-            break;
-        }
-        void* post;
-        if (es < PV_STAGE_MLP_POST) {
-        void* ln2 = nullptr;
-        if (es < PV_STAGE_LN2) {
-        // ln2 (block :130)
-        ln2 = pick(PV_SLOT_LN2_OUT, l, ws.ln_out);
-        {
-            LnParams L = {};
-            L.x = resid_mid; L.ldx = dm; L.rows = M; L.d = dm; L.eps = d.eps; L.do_ln = 1;
-            L.w = W.ln2_w; L.b = W.ln2_b;
-            L.scale_out = (float*)tap_at(PV_SLOT_LN2_SCALE, l);
-            L.norm_f32_out = (float*)tap_at(PV_SLOT_LN2_NORM_F32, l);
-            L.out = ln2;
-            if ((rc = pv_launch_ln(dt, L, stream))) return rc;
-        }
-        } else if (es == PV_STAGE_LN2) {
-            if (bf16) {
-                ln2 = wsb + ws.ln_out;
-                if ((rc = pv_launch_cast_from_f32(dt, (const float*)act_in[0], ln2, (int64_t)M * dm, stream))) return rc;
-            } else {
-                ln2 = const_cast<void*>(act_in[0]);
-            }
-        }
-        if (xs == PV_STAGE_LN2) break;
-        post = pick(PV_SLOT_MLP_POST, l, ws.mlp_post);
-        if (es < PV_STAGE_MLP_PRE) {
-        // mlp (mlp.py:65-80): pre -> act -> post
-        {
-            GemmParams g = {};
-            g.A = ln2; g.lda = dm; g.a_mode = PV_A_PLAIN; g.Bt = S.WinT; g.ldb = dm;
-            g.M = M; g.N = dmlp; g.K = dm; g.epi = PV_EPI_ACT; g.act = d.activation; g.bias0 = W.b_in;
-            g.out0 = tap_at(PV_SLOT_MLP_PRE, l); g.out1 = post; g.ldo = dmlp;
-            if ((rc = pv_launch_gemm(dt, g, stream))) return rc;
-        }
-        } else {
-            // behind a hooked mlp.hook_pre: the activation function on the edited pre-activation (mlp.py:67-72)
-            if ((rc = pv_launch_act(dt, d.activation, act_in[0], post, (int64_t)M * dmlp, stream))) return rc;
-        }
-        if (xs == PV_STAGE_MLP_PRE) break;
-        } else {
-            post = const_cast<void*>(act_in[0]);
-        }
-        if (xs == PV_STAGE_MLP_POST) break;
-        // mlp_out ; resid_post = resid_mid + mlp_out (block :131-134)
-        void* resid_post = tap_at(PV_SLOT_RESID_POST, l);
-        if (!resid_post) {
-            // the workspace buffer NOT holding resid_pre (resid_pre is dead after the O-proj, but keep
-            // it simple and safe: ping-pong)
-            resid_post = wsb + (resid_in_a ? ws.resid_b : ws.resid_a);
-            resid_in_a = !resid_in_a;
-        }
-        {
-            GemmParams g = {};
-            g.A = post; g.lda = dmlp; g.a_mode = PV_A_PLAIN; g.Bt = S.WoutT; g.ldb = dmlp;
-            g.M = M; g.N = dm; g.K = dmlp; g.epi = PV_EPI_RESID; g.bias0 = W.b_out;
-            g.out0 = tap_at(PV_SLOT_MLP_OUT, l); g.out1 = resid_post; g.ldo = dm; g.resid = resid_mid; g.ldr = dm;
-            if ((rc = pv_launch_gemm(dt, g, stream))) return rc;
-        }
-        resid = resid_post;
-    }
-    if (!run_head) return PV_OK;
+// ---- token + position embedding (base_text_transformer.py:125-143): hook_embed is the gather itself, hook_full_embed the residual
+// stream entering block 0
+int embed_text(Fwd& F, void*& resid) {
+    resid = F.pick(PV_SLOT_FULL_EMBED, 0, F.ws.resid_a);
+    return pv_launch_token_embed(F.dt, F.s.tokens, F.p->token_embed, F.p->pos_embed, F.tap_at(PV_SLOT_EMBED, 0), resid, F.B, F.T,
+                                 F.d.d_model, F.p->vocab, F.stream);
+}
 
-    // ---- ln_final on all tokens only if one of its taps is requested or the pooling reads them all, else on the CLS rows only
-    // (a text plan: on the EOT rows only)
-    const bool lnf_all = d.pooling != PV_POOL_CLS || tap_at(PV_SLOT_LNF_SCALE, 0) || tap_at(PV_SLOT_LNF_NORM_F32, 0) || tap_at(PV_SLOT_LNF_OUT, 0);
-    void* lnf = pick(PV_SLOT_LNF_OUT, 0, ws.lnf);
-    int64_t lnf_ld;   // row stride (elements) between CLS rows of consecutive images
-    {
-        LnParams L = {};
-        L.x = resid; L.d = dm; L.eps = d.eps; L.do_ln = 1; L.w = p->w.ln_final_w; L.b = p->w.ln_final_b;
-        if (lnf_all) {
-            L.ldx = dm; L.rows = M;
-            L.scale_out = (float*)tap_at(PV_SLOT_LNF_SCALE, 0);
-            L.norm_f32_out = (float*)tap_at(PV_SLOT_LNF_NORM_F32, 0);
-            lnf_ld = (int64_t)T * dm;
-        } else if (p->is_text) {
-            // the residual rows at the EOT tokens first (base_text_transformer.py:151), LayerNorm on those B rows
-            void* rows = wsb + ws.pooled;
-            if ((rc = pv_launch_eot_rows(dt, tokens, resid, rows, B, T, dm, stream))) return rc;
-            L.x = rows; L.ldx = dm; L.rows = B;
-            lnf_ld = dm;
-        } else {
-            L.ldx = (int64_t)T * dm; L.rows = B;
-            lnf_ld = dm;
-        }
-        L.out = lnf;
-        if ((rc = pv_launch_ln(dt, L, stream))) return rc;
+// ---- the block's steps (transformer_block.py:80-138) -----------------------------------------
+// ln1 (transformer_block.py:106-109) and ln2 (:130) (layer_norm.py:75-93); scale_slot: PV_SLOT_LN1_SCALE | PV_SLOT_LN2_SCALE.  Both share
+// ln_out.  hooked: behind a hooked .hook_scale / .hook_normalized the (edited) fp32 normalized tensor act_in[0] is rounded to the storage
+// dtype like the module's own last step (layer_norm.py:93) -- into the workspace, never into a tap
+int block_ln(Fwd& F, int l, int scale_slot, const void* w, const void* b, const void* x, bool hooked, void*& out) {
+    static_assert(PV_SLOT_LN1_NORM_F32 == PV_SLOT_LN1_SCALE + 1 && PV_SLOT_LN1_OUT == PV_SLOT_LN1_SCALE + 2 &&
+                  PV_SLOT_LN2_NORM_F32 == PV_SLOT_LN2_SCALE + 1 && PV_SLOT_LN2_OUT == PV_SLOT_LN2_SCALE + 2, "a LayerNorm's three slots");
+    const int dm = F.d.d_model;
+    if (hooked) {
+        out = F.bf16 ? (void*)(F.wsb + F.ws.ln_out) : const_cast<void*>(F.act_in[0]);
+        return F.bf16 ? pv_launch_cast_from_f32(F.dt, (const float*)F.act_in[0], out, (int64_t)F.M * dm, F.stream) : PV_OK;
     }
-    // ---- pooled row (base_vit.py:195-208) -> head (head.py:27-37) -> hook_post_head_pre_normalize -> F.normalize
+    out = F.pick(scale_slot + 2, l, F.ws.ln_out);
+    LnParams L = {};
+    L.x = x; L.ldx = dm; L.rows = F.M; L.d = dm; L.eps = F.d.eps; L.do_ln = 1;
+    L.w = w; L.b = b;
+    L.scale_out = (float*)F.tap_at(scale_slot, l);
+    L.norm_f32_out = (float*)F.tap_at(scale_slot + 1, l);
+    L.out = out;
+    return pv_launch_ln(F.dt, L, F.stream);
+}
+
+// q, k, v (attention.py:186-244) as one GEMM against the packed [3*H*dh][d] shadow
+int block_qkv(Fwd& F, int l, const void* ln1, void*& q, void*& k, void*& v) {
+    const pv_vit_layer_weights& W = F.p->lw[l];
+    const int dm = F.d.d_model, HD = F.p->HD;
+    q = F.pick(PV_SLOT_Q, l, F.ws.q);
+    k = F.pick(PV_SLOT_K, l, F.ws.k);
+    v = F.pick(PV_SLOT_V, l, F.ws.v);
+    GemmParams g = linear(ln1, dm, F.p->sh[l].Wqkv, dm, F.M, 3 * HD, dm, PV_EPI_QKV);
+    g.nsplit = HD;
+    g.bias0 = W.b_Q; g.bias1 = W.b_K; g.bias2 = W.b_V; g.out0 = q; g.out1 = k; g.out2 = v; g.ldo = HD;
+    return pv_launch_gemm(F.dt, g, F.stream);
+}
+
+// scores / pattern / z (attention.py:135-152, 246-281): the whole core from q, k, v (es < PV_STAGE_SCORES) -- or, behind a hooked
+// hook_attn_scores / hook_pattern (es = that stage), the rest of it from the edited tensor act_in[0] and v = act_in[1]
+int block_attention(Fwd& F, int l, int es, const void* q, const void* k, const void* v, void*& z) {
+    z = F.pick(PV_SLOT_Z, l, F.ws.z);
+    AttnParams a = {};
+    a.z = z;
+    a.B = F.B; a.T = F.T; a.H = F.d.n_heads; a.dh = F.d.d_head; a.attn_scale = F.d.attn_scale;
+    if (es < PV_STAGE_SCORES) {
+        a.q = q; a.k = k; a.v = v;
+        a.scores = F.tap_at(PV_SLOT_SCORES, l); a.pattern = F.tap_at(PV_SLOT_PATTERN, l);
+        a.causal = F.p->causal;
+        return pv_launch_attention(F.dt, a, F.stream);
+    }
+    a.v = F.act_in[1];
+    if (es == PV_STAGE_SCORES) { a.scores = const_cast<void*>(F.act_in[0]); a.pattern = F.tap_at(PV_SLOT_PATTERN, l); }
+    else a.pattern = const_cast<void*>(F.act_in[0]);
+    return pv_launch_attention_resume(F.dt, a, es == PV_STAGE_SCORES ? 1 : 0, F.stream);
+}
+
+// attn_out = z W_O + b_O ; resid_mid = resid_pre + attn_out (attention.py:155-167 ; block :117-124)
+int block_oproj(Fwd& F, int l, const void* z, const void* resid_pre, void*& resid_mid) {
+    const int dm = F.d.d_model, HD = F.p->HD;
+    resid_mid = F.pick(PV_SLOT_RESID_MID, l, F.ws.resid_mid);
+    GemmParams g = linear(z, HD, F.p->sh[l].WoT, HD, F.M, dm, HD, PV_EPI_RESID);
+    g.bias0 = F.p->lw[l].b_O;
+    g.out0 = F.tap_at(PV_SLOT_ATTN_OUT, l); g.out1 = resid_mid; g.ldo = dm; g.resid = resid_pre; g.ldr = dm;
+    return pv_launch_gemm(F.dt, g, F.stream);
+}
+
+// mlp (mlp.py:65-80): pre -> act -> post as one GEMM -- or, behind a hooked mlp.hook_pre (pre_hooked), the activation function alone
+// on the edited pre-activation act_in[0] (mlp.py:67-72)
+int block_mlp_in(Fwd& F, int l, bool pre_hooked, const void* ln2, void*& post) {
+    const int dm = F.d.d_model, dmlp = F.d.d_mlp;
+    post = F.pick(PV_SLOT_MLP_POST, l, F.ws.mlp_post);
+    if (pre_hooked) return pv_launch_act(F.dt, F.d.activation, F.act_in[0], post, (int64_t)F.M * dmlp, F.stream);
+    GemmParams g = linear(ln2, dm, F.p->sh[l].WinT, dm, F.M, dmlp, dm, PV_EPI_ACT);
+    g.act = F.d.activation; g.bias0 = F.p->lw[l].b_in;
+    g.out0 = F.tap_at(PV_SLOT_MLP_PRE, l); g.out1 = post; g.ldo = dmlp;
+    return pv_launch_gemm(F.dt, g, F.stream);
+}
+
+// mlp_out ; resid_post = resid_mid + mlp_out (block :131-134), which becomes the residual stream
+int block_mlp_out(Fwd& F, int l, const void* post, const void* resid_mid, void*& resid) {
+    const int dm = F.d.d_model, dmlp = F.d.d_mlp;
+    void* resid_post = F.tap_at(PV_SLOT_RESID_POST, l);
+    if (!resid_post) {
+        // the workspace buffer NOT holding resid_pre (resid_pre is dead after the O-proj, but keep it simple and safe: ping-pong)
+        resid_post = F.wsb + (F.resid_in_a ? F.ws.resid_b : F.ws.resid_a);
+        F.resid_in_a = !F.resid_in_a;
+    }
+    GemmParams g = linear(post, dmlp, F.p->sh[l].WoutT, dmlp, F.M, dm, dmlp, PV_EPI_RESID);
+    g.bias0 = F.p->lw[l].b_out;
+    g.out0 = F.tap_at(PV_SLOT_MLP_OUT, l); g.out1 = resid_post; g.ldo = dm; g.resid = resid_mid; g.ldr = dm;
+    resid = resid_post;
+    return pv_launch_gemm(F.dt, g, F.stream);
+}
+
+// Block l of a segment, stage by stage in PV_STAGE_* order.  es: the stage the block is entered at (PV_STAGE_ENTRY: its start): a stage
+// before es is skipped, the one AT es adopts the caller's act_in, every later one is computed here.  xs: the stage the segment stops
+// at inside this block (PV_STAGE_ENTRY: it runs through).  `resid` is the residual stream the rest of the block adds to -- resid_pre,
+// or resid_mid when es >= PV_STAGE_MID -- and leaves as resid_post (an exit at PV_STAGE_MID: as resid_mid; any other exit: unchanged).
+int run_block(Fwd& F, int l, int es, int xs, void*& resid) {
+    const pv_vit_layer_weights& W = F.p->lw[l];
+    void *ln1 = nullptr, *q = nullptr, *k = nullptr, *v = nullptr, *z = nullptr, *resid_mid = nullptr, *ln2 = nullptr, *post = nullptr;
+    int rc = PV_OK;
+    if (es <= PV_STAGE_LN1) rc = block_ln(F, l, PV_SLOT_LN1_SCALE, W.ln1_w, W.ln1_b, resid, es == PV_STAGE_LN1, ln1);
+    if (rc || xs == PV_STAGE_LN1) return rc;
+
+    if (es < PV_STAGE_QKV) rc = block_qkv(F, l, ln1, q, k, v);
+    else if (es == PV_STAGE_QKV) { q = const_cast<void*>(F.act_in[0]); k = const_cast<void*>(F.act_in[1]); v = const_cast<void*>(F.act_in[2]); }
+    if (rc || xs == PV_STAGE_QKV) return rc;
+
+    // scores, pattern and z are one kernel: an exit at any of the three runs the whole core first
+    if (es <= PV_STAGE_PATTERN) rc = block_attention(F, l, es, q, k, v, z);
+    else if (es == PV_STAGE_Z) z = const_cast<void*>(F.act_in[0]);
+    if (rc || xs == PV_STAGE_SCORES || xs == PV_STAGE_PATTERN || xs == PV_STAGE_Z) return rc;
+
+    if (es < PV_STAGE_MID) rc = block_oproj(F, l, z, resid, resid_mid);
+    else resid_mid = resid;
+    if (xs == PV_STAGE_MID) resid = resid_mid;
+    if (rc || xs == PV_STAGE_MID) return rc;
+
+    if (es <= PV_STAGE_LN2) rc = block_ln(F, l, PV_SLOT_LN2_SCALE, W.ln2_w, W.ln2_b, resid_mid, es == PV_STAGE_LN2, ln2);
+    if (rc || xs == PV_STAGE_LN2) return rc;
+
+    // mlp pre and post are one GEMM
+    if (es <= PV_STAGE_MLP_PRE) rc = block_mlp_in(F, l, es == PV_STAGE_MLP_PRE, ln2, post);
+    else post = const_cast<void*>(F.act_in[0]);
+    if (rc || xs == PV_STAGE_MLP_PRE || xs == PV_STAGE_MLP_POST) return rc;
+
+    return block_mlp_out(F, l, post, resid_mid, resid);
+}
+
+// ---- ln_final on all tokens only if one of its taps is requested or the pooling reads them all (lnf_all), else on the CLS rows only
+// (a text plan: on the EOT rows only).  lnf_ld: the row stride (elements) between the pooled rows of consecutive images
+int head_ln_final(Fwd& F, const void* resid, bool lnf_all, void*& lnf, int64_t& lnf_ld) {
+    const int dm = F.d.d_model;
+    lnf = F.pick(PV_SLOT_LNF_OUT, 0, F.ws.lnf);
+    LnParams L = {};
+    L.x = resid; L.d = dm; L.eps = F.d.eps; L.do_ln = 1; L.w = F.p->w.ln_final_w; L.b = F.p->w.ln_final_b; L.out = lnf;
+    lnf_ld = lnf_all ? (int64_t)F.T * dm : dm;
+    if (lnf_all) {
+        L.ldx = dm; L.rows = F.M;
+        L.scale_out = (float*)F.tap_at(PV_SLOT_LNF_SCALE, 0);
+        L.norm_f32_out = (float*)F.tap_at(PV_SLOT_LNF_NORM_F32, 0);
+    } else if (F.p->is_text) {
+        // the residual rows at the EOT tokens first (base_text_transformer.py:151), LayerNorm on those B rows
+        void* rows = F.wsb + F.ws.pooled;
+        int rc;
+        if ((rc = pv_launch_eot_rows(F.dt, F.s.tokens, resid, rows, F.B, F.T, dm, F.stream))) return rc;
+        L.x = rows; L.ldx = dm; L.rows = F.B;
+    } else {
+        L.ldx = (int64_t)F.T * dm; L.rows = F.B;
+    }
+    return pv_launch_ln(F.dt, L, F.stream);
+}
+
+// ---- ln_final -> pooled row (base_vit.py:195-208) -> head (head.py:27-37) -> hook_post_head_pre_normalize -> F.normalize
+int head(Fwd& F, const void* resid) {
+    const pv_vit_plan* p = F.p;
+    const pv_vit_desc& d = F.d;
+    const int dm = d.d_model, B = F.B, T = F.T, dt = F.dt;
+    void* const out = F.s.out;
+    const bool lnf_all = d.pooling != PV_POOL_CLS || F.tap_at(PV_SLOT_LNF_SCALE, 0) || F.tap_at(PV_SLOT_LNF_NORM_F32, 0) || F.tap_at(PV_SLOT_LNF_OUT, 0);
+    void* lnf;
+    int64_t lnf_ld;
+    int rc;
+    if ((rc = head_ln_final(F, resid, lnf_all, lnf, lnf_ld))) return rc;
     const bool cls_mean = d.pooling == PV_POOL_CLS_MEAN;
     const int nout = d.has_head ? d.n_classes : (cls_mean ? 2 * dm : dm);
-    void* head_tap = tap_at(PV_SLOT_HEAD_OUT, 0);
-    void* hb = head_tap ? head_tap : (d.normalize_output ? (void*)(wsb + ws.head) : out);
+    void* head_tap = F.tap_at(PV_SLOT_HEAD_OUT, 0);
+    void* hb = head_tap ? head_tap : (d.normalize_output ? (void*)(F.wsb + F.ws.head) : out);
     if (p->is_text && lnf_all) {
         // x[arange(B), tokens.argmax(dim=-1)] of the ln_final output (base_text_transformer.py:151)
-        void* pooled = wsb + ws.pooled;
-        if ((rc = pv_launch_eot_rows(dt, tokens, lnf, pooled, B, T, dm, stream))) return rc;
+        void* pooled = F.wsb + F.ws.pooled;
+        if ((rc = pv_launch_eot_rows(dt, F.s.tokens, lnf, pooled, B, T, dm, F.stream))) return rc;
         lnf = pooled;
         lnf_ld = dm;
     }
     if (d.pooling != PV_POOL_CLS) {
         // "gaap": the mean over all tokens feeds the head (or IS the output); dino-vitb: [B, d, 2] = (cls, mean over the patches)
-        void* pooled = (d.has_head) ? (void*)(wsb + ws.pooled) : hb;
-        if ((rc = pv_launch_token_mean(dt, lnf, pooled, B, T, dm, cls_mean ? 1 : 0, cls_mean ? 1 : 0, stream))) return rc;
+        void* pooled = (d.has_head) ? (void*)(F.wsb + F.ws.pooled) : hb;
+        if ((rc = pv_launch_token_mean(dt, lnf, pooled, B, T, dm, cls_mean ? 1 : 0, cls_mean ? 1 : 0, F.stream))) return rc;
         lnf = pooled;
         lnf_ld = dm;
     }
     if (d.has_head) {
-        GemmParams g = {};
-        g.A = lnf; g.lda = lnf_ld; g.a_mode = PV_A_PLAIN; g.Bt = p->WhT; g.ldb = dm;
-        g.M = B; g.N = nout; g.K = dm; g.epi = PV_EPI_BIAS; g.bias0 = p->w.b_H; g.out0 = hb; g.ldo = nout;
-        if ((rc = pv_launch_gemm(dt, g, stream))) return rc;
+        GemmParams g = linear(lnf, lnf_ld, p->WhT, dm, B, nout, dm, PV_EPI_BIAS);
+        g.bias0 = p->w.b_H; g.out0 = hb; g.ldo = nout;
+        if ((rc = pv_launch_gemm(dt, g, F.stream))) return rc;
     } else if (d.pooling == PV_POOL_CLS) {
         PV_HIP_CHECK(hipMemcpy2DAsync(hb, (size_t)dm * p->EB, lnf, (size_t)lnf_ld * p->EB, (size_t)dm * p->EB, B,
-                                      hipMemcpyDeviceToDevice, stream));
+                                      hipMemcpyDeviceToDevice, F.stream));
     }
     if (d.normalize_output) {
         // dim = -1 of [B, d, 2] is the (cls, mean) pair of one channel (base_vit.py:214-215 on the concatenated tensor)
-        if ((rc = cls_mean ? pv_launch_l2norm(dt, hb, out, B * dm, 2, stream) : pv_launch_l2norm(dt, hb, out, B, nout, stream))) return rc;
-    } else if (hb != out) {
-        PV_HIP_CHECK(hipMemcpyAsync(out, hb, (size_t)B * nout * p->EB, hipMemcpyDeviceToDevice, stream));
+        return cls_mean ? pv_launch_l2norm(dt, hb, out, B * dm, 2, F.stream) : pv_launch_l2norm(dt, hb, out, B, nout, F.stream);
     }
+    if (hb != out) PV_HIP_CHECK(hipMemcpyAsync(out, hb, (size_t)B * nout * p->EB, hipMemcpyDeviceToDevice, F.stream));
     return PV_OK;
+}
+
+// validate -> context -> embed (or adopt resid_in: a resumed forward skips the embedding) -> blocks -> head
+int run_segment(const pv_vit_plan* p, const Segment& s) {
+    Workspace ws;
+    int rc;
+    if ((rc = check_segment(p, s, ws))) return rc;
+    Fwd F(p, s, ws);
+    if ((rc = F.set_taps(s.taps, s.n_taps))) return rc;
+    void* resid = const_cast<void*>(s.resid_in);
+    if (!resid && (rc = p->is_text ? embed_text(F, resid) : embed_vision(F, resid))) return rc;
+    // blocks [first_block, end_block) in full; with exit_stage also block end_block up to it; with entry_stage the first block resumes behind it
+    const int last_block = s.exit_stage ? s.end_block + 1 : s.end_block;
+    for (int l = s.first_block; l < last_block; ++l)
+        if ((rc = run_block(F, l, l == s.first_block ? s.entry_stage : PV_STAGE_ENTRY, l == s.end_block ? s.exit_stage : PV_STAGE_ENTRY, resid))) return rc;
+    return s.run_head ? head(F, resid) : PV_OK;
 }
 }  // namespace
 
+extern "C" int pv_vit_forward(pv_vit_plan* p, const void* images, int32_t B, int32_t n_blocks, int32_t run_head, const pv_tap* taps,
+                              int32_t n_taps, void* workspace, size_t workspace_bytes, void* out, void* stream) {
+    PV_REQUIRE(images, "null argument");
+    Segment s = segment_io(B, run_head, taps, n_taps, workspace, workspace_bytes, out, stream);
+    s.images = images; s.end_block = n_blocks;
+    return run_segment(p, s);
+}
+
+extern "C" int pv_vit_forward_stage(pv_vit_plan* p, const void* images, const void* resid_in, const void* act_in0, const void* act_in1,
+                                    const void* act_in2, int32_t B, int32_t first_block, int32_t entry_stage, int32_t end_block,
+                                    int32_t exit_stage, int32_t run_head, const pv_tap* taps, int32_t n_taps, void* workspace,
+                                    size_t workspace_bytes, void* out, void* stream) {
+    Segment s = segment_io(B, run_head, taps, n_taps, workspace, workspace_bytes, out, stream);
+    s.images = images; s.resid_in = resid_in;
+    s.act_in[0] = act_in0; s.act_in[1] = act_in1; s.act_in[2] = act_in2;
+    s.first_block = first_block; s.entry_stage = entry_stage; s.end_block = end_block; s.exit_stage = exit_stage;
+    return run_segment(p, s);
+}
+
 extern "C" int pv_text_forward(pv_vit_plan* p, const int64_t* tokens, int32_t B, int32_t run_head, const pv_tap* taps, int32_t n_taps,
-                               void* workspace, size_t workspace_bytes, void* out, void* stream_) {
+                               void* workspace, size_t workspace_bytes, void* out, void* stream) {
     PV_REQUIRE(p && tokens, "null argument");
-    PV_REQUIRE(p->is_text, "pv_text_forward needs a plan of pv_text_plan_create (a vision plan runs through pv_vit_forward*)");
-    return vit_forward_impl(p, nullptr, tokens, nullptr, nullptr, B, 0, 0, p->d.n_layers, 0, run_head, taps, n_taps, workspace,
-                            workspace_bytes, out, stream_);
+    Segment s = segment_io(B, run_head, taps, n_taps, workspace, workspace_bytes, out, stream);
+    s.tokens = tokens; s.end_block = p->d.n_layers;
+    return run_segment(p, s);
 }
 
 // ---- kernel-level entry points -------------------------------------------------------------

@@ -12,6 +12,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import torch
 
 from . import _native as N
+from .split_plan import EXIT, KIND
 from .tap_plan import TapSpec, final_residual_name, head_out_shape, hook_order, pooling_mode, tap_spec
 
 _ALIGN = 256
@@ -325,13 +326,12 @@ class NativeViT:
         the arena as usual and the caller copies.
         With ``resid_in`` ([B, T, d_model]) the forward is RESUMED at block ``first_block`` from that residual
         (``images`` is ignored, names of earlier stages must not be requested).  Positions inside a block
-        (``entry_stage`` / ``exit_stage``, pv_vit_forward_stage; PV_STAGE_*): 0 block entry, 1 ln1 taken, 2 q / k / v ready,
-        3 attention scores, 4 pattern, 5 z ready, 6 after the attention half, 7 ln2 taken,
-        8 mlp pre ready, 9 mlp post ready.  A segment that exits at a stage runs block ``n_blocks`` up to it; one that enters at a
-        stage gets the residual stream the rest of the block adds to in ``resid_in`` and the (hook-edited) activations of the stage
-        in ``act_in``: (normalized fp32,) | (q, k, v) | (scores, v) | (pattern, v) | (z,) | (normalized fp32,) | (pre,) | (post,).
-        Returns (model_out, {name: tensor}); for an exit inside the attention half or the MLP model_out is the stage's (first)
-        activation."""
+        (``entry_stage`` / ``exit_stage``, pv_vit_forward_stage): the PV_STAGE_* numbers, named and described by the two tables of
+        split_plan (``ENTRY`` .. ``MLP_POST``; ``EXIT[stage]``).  A segment that exits at a stage runs block ``n_blocks`` up to it; one
+        that enters at a stage gets the residual stream the rest of the block adds to (``EXIT[stage].carried``) in ``resid_in`` and
+        the (hook-edited) activations of the stage in ``act_in``: the kinds of ``EXIT[stage].acts``, fp32 at the LayerNorm stages.
+        Returns (model_out, {name: tensor}); for an exit inside a block model_out is the stage's first activation
+        (``EXIT[stage].acts[0]``; behind the attention half, which hands on no activation, hook_resid_mid)."""
         entry_stage, exit_stage = int(entry_stage), int(exit_stage)
         cfg = self.cfg
         T = self.n_tokens
@@ -358,21 +358,17 @@ class NativeViT:
             specs = {n: tap_spec(n, cfg, B, T) for n in names}
         out_name = None if layout is None else out_name
         if layout is None and not run_head:
-            out_name = {0: None, 1: f"blocks.{n_blocks}.ln1.hook_normalized", 2: f"blocks.{n_blocks}.attn.hook_q",
-                        3: f"blocks.{n_blocks}.attn.hook_attn_scores", 4: f"blocks.{n_blocks}.attn.hook_pattern",
-                        5: f"blocks.{n_blocks}.attn.hook_z", 6: f"blocks.{n_blocks}.hook_resid_mid",
-                        7: f"blocks.{n_blocks}.ln2.hook_normalized", 8: f"blocks.{n_blocks}.mlp.hook_pre",
-                        9: f"blocks.{n_blocks}.mlp.hook_post"}[exit_stage] \
-                or final_residual_name(cfg, n_blocks)
+            ex = EXIT[exit_stage]
+            out_name = f"blocks.{n_blocks}.{KIND[(ex.acts or ex.taps)[0]].sub}" if exit_stage else final_residual_name(cfg, n_blocks)
             if out_name not in specs:
                 specs[out_name] = tap_spec(out_name, cfg, B, T)
         acts = []
-        act_dtype = torch.float32 if entry_stage in (1, 7) else cfg.dtype      # (the LayerNorm points carry fp32 in either mode)
+        act_dtype = torch.float32 if EXIT[entry_stage].ln else cfg.dtype      # (the LayerNorm points carry fp32 in either mode)
         for t in act_in:
             if t.device != self.device:
                 raise N.NativeError(f"activation on {t.device}, model on {self.device}")
             acts.append(t.to(act_dtype).contiguous())
-        want_acts = {0: 0, 1: 1, 2: 3, 3: 2, 4: 2, 5: 1, 6: 0, 7: 1, 8: 1, 9: 1}[entry_stage]
+        want_acts = len(EXIT[entry_stage].acts)
         if len(acts) != want_acts:
             raise ValueError(f"entry_stage {entry_stage} takes {want_acts} activation tensors, got {len(acts)}")
         # unique buffers -> slab offsets
