@@ -1,6 +1,6 @@
 """A CPU stand-in with NativeSAE's interface, built from the oracle (test infrastructure only).
 
-The data-parallel orchestration of ``VisionSAETrainer._native_dp_step`` -- which collective moves what, which rows a rank
+The data-parallel orchestration of ``VisionSAETrainer._step_topk`` -- which collective moves what, which rows a rank
 clips / projects / updates, when the parameter all-gathers are waited for -- is plain host code around the engine's
 methods.  This twin lets that code run under gloo on CPU (world 2 and 4) where the HIP engine cannot."""
 from typing import Optional

@@ -1,5 +1,5 @@
 """The data-parallel SAE step with a feature-sharded optimizer on CPU: the trainer's own
-``_native_dp_step`` -- global batch mean all-reduce, reduce-scatter of the gradient rows, one small bucket (gb_dec | fire
+``_step_topk`` -- global batch mean all-reduce, reduce-scatter of the gradient rows, one small bucket (gb_dec | fire
 counts | loss, mse, l0), scalar all-reduce of the ranks' clip-norm terms, clip / project / Adam on the rank's rows only,
 asynchronous all-gather of the parameter rows -- runs under gloo with world 2 and world 4 around a CPU engine built from
 the oracle (tests/_cpu_engine.py), and must land on the single-process oracle's parameters, losses and statistics."""
@@ -47,7 +47,7 @@ def _worker(rank, world, port, q, b_dec_init):
     tr = VisionSAETrainer(cfg, model=None, dataset=None, sparse_coder=sae).use_feature_parallel(False)     # the data-parallel mode
     assert tr.world == world and tr._shard(D_SAE) == (rank * D_SAE // world, (rank + 1) * D_SAE // world)
     # run the trainer's native branch on the CPU twin of the engine
-    tr._native_ok = lambda *a, **k: True
+    tr._native_kind = lambda *a, **k: "topk"
     real_get = VisionSAETrainer._get_engine
 
     def get_engine(s, n_tokens):
@@ -106,7 +106,7 @@ def test_sharded_optimizer_step_equals_single_process_oracle(world):
         assert frac == STEPS * N
 
 
-# ---- ReLU + L1 on the dense step, data parallel (VisionSAETrainer._native_dense_step with a process group): tokens sharded, the
+# ---- ReLU + L1 on the dense step, data parallel (VisionSAETrainer._step_dense with a process group): tokens sharded, the
 # global batch mean all-reduced, ONE all-reduce of the flat gradient buffer + one small bucket (fire counts | loss, mse, l0, -, l1),
 # replicated optimizer
 L1C = 2e-3
@@ -267,7 +267,7 @@ def test_gated_data_parallel_step_equals_single_process_oracle(topk):
         assert np.array_equal(act, stats["act_freq_scores"]) and np.array_equal(since, stats["n_fwd_since_fired"])
 
 
-# ---- top-k Transcoder, data parallel: VisionSAETrainer._native_dp_step's transcoder branch (the TARGET's global mean, one all-reduce
+# ---- top-k Transcoder, data parallel: VisionSAETrainer._step_topk with a transcoder engine (the TARGET's global mean, one all-reduce
 # of the whole flat gradient buffer -- b_dec_out and W_skip ride in it -- replicated optimizer)
 def _tc_init():
     init = dict(synth_sae_state(D_IN, D_SAE, 0))
@@ -354,7 +354,7 @@ def test_topk_transcoder_data_parallel_step_equals_single_process_oracle():
 
 # ---- ghost gradients with a process group (use_ghost_grads; sae.py:151-179): the ghost term's two batch-wide quantities -- the residual's
 # column mean (:156) and the mse loss (:172) -- are exchanged between the step and the ghost term (top-k) / after a pass without it
-# (dense ReLU step): VisionSAETrainer._native_dp_step / _native_dense_step at world 2 against the single-process oracle
+# (dense ReLU step): VisionSAETrainer._step_topk / _step_dense at world 2 against the single-process oracle
 def _ghost_worker(rank, world, port, q, relu):
     import torch.distributed as dist
     from vit_prisma_amd.sae import StandardSparseAutoencoder, VisionModelSAERunnerConfig, VisionSAETrainer

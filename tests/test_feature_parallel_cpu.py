@@ -147,7 +147,7 @@ def _trainer_worker(rank, world, port, q, drop=False):
             for n, v in synth_sae_state(D_IN, D_SAE, 0).items():
                 getattr(sae, n).copy_(torch.from_numpy(v))
     tr = VisionSAETrainer(cfg, model=None, dataset=None, sparse_coder=sae).use_feature_parallel(True, drop_replicas=drop)
-    tr._native_ok = lambda *a, **k: True
+    tr._native_kind = lambda *a, **k: "topk"
     tr._make_shard_engine = lambda s, max_tokens: (lambda We, Wd, be, bd: OracleShardEngine(We, Wd, be, bd, K, max_tokens))
     act, since, frac, opt, sched = tr.initialize_training_variables()
     losses = []

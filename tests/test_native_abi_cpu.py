@@ -52,3 +52,11 @@ def test_plan_queries_and_error_reporting_without_gpu():
     assert lib.pv_sae_plan_create(C.byref(sdesc), C.byref(splan)) == 1
     sdesc.k, sdesc.d_in = 32, 1284
     assert lib.pv_sae_plan_create(C.byref(sdesc), C.byref(splan)) == 1
+
+
+def test_sae_flag_constants_equal_the_header():
+    """The PV_SAE_* constants NativeSAE composes its flag words from are the header's, every one of them."""
+    src = open(os.path.join(ROOT, "include", "pv_native.h")).read()
+    header = {name: int(value) for name, value in re.findall(r"^#define (PV_SAE_[A-Z0-9_]+) (\d+)\b", src, flags=re.M)}
+    assert len(header) >= 8 and header["PV_SAE_FUSED_SQNORM"] == 32
+    assert header == {n: v for n, v in vars(_native).items() if n.startswith("PV_SAE_")}

@@ -86,7 +86,7 @@ def _dp_worker(rank, world, port, q):
     O.renorm_decoder(P)
     x = synth_sae_batch(N, d_in, seed=0)
     xs = x[rank * (N // world):(rank + 1) * (N // world)]
-    # the two pre-reductions of SURVEY.md 8e, exactly as VisionSAETrainer._native_step issues them
+    # the two pre-reductions of SURVEY.md 8e, exactly as VisionSAETrainer._step_topk issues them
     bm = torch.from_numpy(xs.sum(axis=0))
     dist.all_reduce(bm)
     fw = O.sae_forward(P, xs, k, batch_mean=(bm / N).numpy(), n_global=N)

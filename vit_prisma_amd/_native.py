@@ -80,6 +80,13 @@ class SaeDesc(C.Structure):
                 ("activation", C.c_int32), ("lp_norm", C.c_float)]
 
 
+# the PV_SAE_* constants of include/pv_native.h under their own names (held equal by tests/test_native_abi_cpu.py): pv_sae_desc.activation,
+# then the flags of the step entry points
+PV_SAE_ACT_RELU, PV_SAE_ACT_TANH_RELU = 0, 1
+PV_SAE_UPDATE_STATS, PV_SAE_RENORM_DECODER, PV_SAE_INV_NORM_VALID, PV_SAE_SPARSE_GRADS = 1, 2, 4, 8
+PV_SAE_TP_ENC_TERM_ONLY, PV_SAE_FUSED_SQNORM = 16, 32
+
+
 class SaeTranscoder(C.Structure):
     """pv_sae_transcoder: all NULL = a plain autoencoder."""
     _fields_ = [(n, C.c_void_p) for n in ("b_dec_out", "gb_dec_out", "mb_dec_out", "vb_dec_out", "W_skip", "gW_skip", "mW_skip",

@@ -86,7 +86,8 @@ class NativeSAE:
         self.params = {n: t.detach() for n, t in self._src.items()}
         desc = N.SaeDesc(d_in=self.d_in, d_sae=self.d_sae, k=self.k, normalize_layer_norm=norm_mode_code(layer_norm),
                          max_tokens=self.max_tokens * (2 if self.gated_topk else 1), ln_eps=ln_eps,
-                         activation={"relu": 0, "topk": 0, "tanh-relu": 1}[activation], lp_norm=float(lp_norm))
+                         activation={"relu": N.PV_SAE_ACT_RELU, "topk": N.PV_SAE_ACT_RELU, "tanh-relu": N.PV_SAE_ACT_TANH_RELU}[activation],
+                         lp_norm=float(lp_norm))
         self._plan = C.c_void_p()
         N.check(self.lib.pv_sae_plan_create(C.byref(desc), C.byref(self._plan)), "pv_sae_plan_create")
         self.filtered_encoder = bool(self.lib.pv_sae_encoder_is_filtered(self._plan))
@@ -161,12 +162,22 @@ class NativeSAE:
         elif self.gated:
             self._gt_scratch = torch.empty(self.lib.pv_sae_gated_scratch_bytes(self._plan, self.max_tokens), dtype=torch.uint8, device=dev)
         self.adam_step = 0
-        self.relu_cap = 256                                        # per-token capacity of relu_step's sparse form
-        self._relu_ws: Optional[torch.Tensor] = None
+        self.relu_cap = 256                                        # per-token capacity of relu_step's / gated_step's sparse form
+        self._relu_ws: Optional[torch.Tensor] = None               # its workspace (_cap_workspace), or the gated form's
+        self._gated_ws: Optional[torch.Tensor] = None
+        self._cap_key: Optional[Tuple[int, int]] = None            # (max_tokens, cap) that workspace was sized for
+        self._relu_last: Optional[Tuple[int, int]] = None          # (tokens, cap) of the last relu_step
+        self._ghost_ws: Optional[torch.Tensor] = None              # workspace of the ghost term, grown on demand
+        self._ghost_keep: tuple = ()                               # the ghost term's small tensors, alive until its kernels have run
+        self._x_pad: Optional[torch.Tensor] = None                 # tc_widths: the input / target rows padded to the common width
+        self._y_pad: Optional[torch.Tensor] = None
+        self._tp: Optional[Tuple[int, int]] = None                 # tp_bind: (first feature of this shard, d_sae of all shards)
+        self._tp_val_kept: Optional[torch.Tensor] = None
         self._shadow_key: Optional[Tuple[int, int]] = None
         self._inv_norm_key: Optional[Tuple[int, int]] = None     # W_dec as the last full-range apply left it (dec_inv_norm is current)
         self._grad_fresh = False                                   # gradient buffers exactly as the last step wrote them
-        self._sq_fused = False
+        self._sq_fused = False                                     # ... and scalars[3] holds the clip norm's sum of squares already
+        self._grad_sparse = False                                  # ... but only the rows of live features (PV_SAE_SPARSE_GRADS)
         # lazy_w_enc: ``apply`` keeps the encoder in W_encT (+ fp16 shadow) only and leaves the parameter's own [d_in, d_sae]
         # layout stale (its transposed write is 75 MB per step at 768 -> 24576); ``materialize_w_enc()`` rewrites it.  The
         # kernels never read that layout.  Off by default: whoever turns it on (VisionSAETrainer, single process) also makes
@@ -239,7 +250,7 @@ class NativeSAE:
             # rows padded to the common width (the step writes the padding columns itself: pv_sae_transcoder.d_out_true)
             if tuple(t.shape) != (x.shape[0], self.tc_widths[1]) or t.device != self.device:
                 raise ValueError(f"target {tuple(t.shape)} on {t.device}: expected [{x.shape[0]}, {self.tc_widths[1]}] on {self.device}")
-            if getattr(self, "_y_pad", None) is None:
+            if self._y_pad is None:
                 self._y_pad = torch.zeros(self.max_tokens, self.d_in, dtype=torch.float32, device=self.device)
             buf = self._y_pad[:x.shape[0]]
             buf[:, :self.tc_widths[1]].copy_(t)
@@ -271,7 +282,7 @@ class NativeSAE:
         if self.tc_widths is not None and x.ndim == 2 and x.shape[1] == self.tc_widths[0] and self.tc_widths[0] < self.d_in:
             if x.shape[0] > self.max_tokens or x.device != self.device:
                 raise ValueError(f"expected [N<={self.max_tokens}, {self.tc_widths[0]}] on {self.device}, got {tuple(x.shape)} on {x.device}")
-            if getattr(self, "_x_pad", None) is None:
+            if self._x_pad is None:
                 self._x_pad = torch.zeros(self.max_tokens, self.d_in, dtype=torch.float32, device=self.device)
             buf = self._x_pad[:x.shape[0]]
             buf[:, :self.tc_widths[0]].copy_(x)                     # (the padding columns stay zero)
@@ -322,6 +333,46 @@ class NativeSAE:
         st = self._state()
         N.check(self.lib.pv_sae_renorm_decoder(self._plan, C.byref(st), self._stream()), "pv_sae_renorm_decoder")
 
+    def _inv_valid(self, renorm_decoder: bool) -> bool:
+        """PV_SAE_INV_NORM_VALID: the last full-range apply left 1 / ||W_dec[j]|| of the rows it wrote; good as long as nobody touched
+        W_dec since."""
+        return bool(renorm_decoder) and self._inv_norm_key is not None and self._inv_norm_key == self._w_dec_key()
+
+    def _begin(self, x: torch.Tensor, target, want_out: bool, batch_mean, n_global, lists: bool):
+        """What every train step does before its call, in this order: the input checked (and padded), the target taken (and padded), an
+        outside edit of W_enc brought into the shadows (the encoder is read as W_encT), then the call's structs.  -> x, its rows, the
+        state, the outputs (lists: with ``topk_idx`` / ``topk_val``), the batch mean as the kernels read it (or None), n_global."""
+        x = self._check_x(x)
+        self._set_target(x, target)
+        self._ensure_shadows()
+        n = x.shape[0]
+        st = self._state()
+        out = N.SaeOut(sae_out=self.sae_out.data_ptr() if want_out else None, topk_idx=self.topk_idx.data_ptr() if lists else None,
+                       topk_val=self.topk_val.data_ptr() if lists else None, scalars=self.scalars.data_ptr(),
+                       fire_count=self.fire_count.data_ptr())
+        return x, n, st, out, self._bm(batch_mean), int(n_global if n_global is not None else n)
+
+    def _left(self, fresh: bool = False, fused: bool = False, sparse: bool = False, inv_norm: bool = False) -> None:
+        """What the call that just returned left behind.  fresh: the gradient buffers are exactly what a step wrote, with the per-feature
+        clip-norm terms beside them (``grad_sqnorm(from_step=True)``); fused: and scalars[3] already (PV_SAE_FUSED_SQNORM); sparse:
+        only the rows of live features were written (PV_SAE_SPARSE_GRADS); inv_norm: ``dec_inv_norm`` still describes W_dec if it did
+        before (a call that renormalises W_dec in place, or may have, leaves it False)."""
+        if not inv_norm:
+            self._inv_norm_key = None
+        self._grad_fresh, self._sq_fused, self._grad_sparse = bool(fresh), bool(fused), bool(sparse)
+
+    def _cap_workspace(self, ws: Optional[torch.Tensor], cap: Optional[int], what: str, size_fn):
+        """The capacity workspace of a sparse form (``relu_step`` / ``gated_step``: an engine runs one of the two), made again when
+        ``cap`` changes.  -> cap, the workspace, its pv_sae_relu_sparse."""
+        cap = int(cap if cap is not None else self.relu_cap)
+        if ws is None or self._cap_key != (self.max_tokens, cap):
+            need = size_fn(self._plan, self.max_tokens, cap)
+            if not need:
+                raise ValueError(f"{what}: cap must be a multiple of 4 in [4, 256], got {cap}")
+            ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            self._cap_key = (self.max_tokens, cap)
+        return cap, ws, N.SaeReluSparse(cap=cap, reserved=0, workspace=ws.data_ptr(), workspace_bytes=ws.numel())
+
     def step(self, x: torch.Tensor, batch_mean: Optional[torch.Tensor] = None, n_global: Optional[int] = None,
              update_stats: bool = True, want_out: bool = False, renorm_decoder: bool = False,
              sparse_grads: bool = False, target: Optional[torch.Tensor] = None, fused_sqnorm: bool = False) -> None:
@@ -333,28 +384,14 @@ class NativeSAE:
         and ``apply`` may follow.  target (transcoder engines): the activation to reconstruct; batch_mean is then ITS mean.
         fused_sqnorm (PV_SAE_FUSED_SQNORM; ignored on transcoders, whose clip norm has more terms): the step's last launch also
         leaves scalars[3], the clip norm's sum of squares -- a following ``grad_sqnorm(from_step=True)`` then has nothing to do."""
-        x = self._check_x(x)
-        self._set_target(x, target)
-        self._ensure_shadows()
-        n = x.shape[0]
-        st = self._state()
-        # the last full-range apply left 1 / ||W_dec[j]|| of the rows it wrote; good as long as nobody touched W_dec since
-        inv_valid = renorm_decoder and self._inv_norm_key is not None and self._inv_norm_key == self._w_dec_key()
-        out = N.SaeOut(sae_out=self.sae_out.data_ptr() if want_out else None, topk_idx=self.topk_idx.data_ptr(),
-                       topk_val=self.topk_val.data_ptr(), scalars=self.scalars.data_ptr(),
-                       fire_count=self.fire_count.data_ptr())
-        bm = None
-        if batch_mean is not None:
-            bm = self._bm(batch_mean)
+        x, n, st, out, bm, ng = self._begin(x, target, want_out, batch_mean, n_global, lists=True)
         fuse = bool(fused_sqnorm) and not self.transcoder and self.d_in <= 4096
-        N.check(self.lib.pv_sae_step(self._plan, C.byref(st), x.data_ptr(), n, bm.data_ptr() if bm is not None else None,
-                                     int(n_global if n_global is not None else n),
-                                     int(bool(update_stats)) | (2 if renorm_decoder else 0) | (4 if inv_valid else 0) |
-                                     (8 if sparse_grads else 0) | (32 if fuse else 0), C.byref(out),
+        N.check(self.lib.pv_sae_step(self._plan, C.byref(st), x.data_ptr(), n, bm.data_ptr() if bm is not None else None, ng,
+                                     N.PV_SAE_UPDATE_STATS * bool(update_stats) | N.PV_SAE_RENORM_DECODER * bool(renorm_decoder) |
+                                     N.PV_SAE_INV_NORM_VALID * self._inv_valid(renorm_decoder) |
+                                     N.PV_SAE_SPARSE_GRADS * bool(sparse_grads) | N.PV_SAE_FUSED_SQNORM * fuse, C.byref(out),
                                      self.workspace.data_ptr(), self.workspace.numel(), self._stream()), "pv_sae_step")
-        self._grad_fresh = True
-        self._grad_sparse = bool(sparse_grads)
-        self._sq_fused = fuse
+        self._left(fresh=True, fused=fuse, sparse=sparse_grads, inv_norm=True)
 
     def dense_step(self, x: torch.Tensor, l1_coefficient: float, batch_mean: Optional[torch.Tensor] = None,
                    n_global: Optional[int] = None, update_stats: bool = True, want_out: bool = False,
@@ -366,25 +403,15 @@ class NativeSAE:
         dead_feature_window`` BEFORE this step, train_sae.py:330-332): adds the ghost residual loss and its gradient
         (sae.py:151-179); costs one device read-back (the number of dead features sizes three small GEMMs).  target: as in ``step``.
         ghost_global: as in ``_ghost_struct`` (required for ghost gradients with n_global > the tokens of this call)."""
-        x = self._check_x(x)
-        self._set_target(x, target)
-        self._ensure_shadows()                                    # (the encoder is read as W_encT: an outside edit of W_enc must reach it)
-        n = x.shape[0]
-        st = self._state()
-        out = N.SaeOut(sae_out=self.sae_out.data_ptr() if want_out else None, topk_idx=None, topk_val=None,
-                       scalars=self.scalars.data_ptr(), fire_count=self.fire_count.data_ptr())
-        bm = self._bm(batch_mean)
+        x, n, st, out, bm, ng = self._begin(x, target, want_out, batch_mean, n_global, lists=False)
         ghost = self._ghost_struct(dead_mask, n, ghost_global) if dead_mask is not None else None
-        N.check(self.lib.pv_sae_dense_step(self._plan, C.byref(st), x.data_ptr(), n, bm.data_ptr() if bm is not None else None,
-                                           int(n_global if n_global is not None else n),
-                                           int(bool(update_stats)) | (2 if renorm_decoder else 0), float(l1_coefficient),
+        N.check(self.lib.pv_sae_dense_step(self._plan, C.byref(st), x.data_ptr(), n, bm.data_ptr() if bm is not None else None, ng,
+                                           N.PV_SAE_UPDATE_STATS * bool(update_stats) | N.PV_SAE_RENORM_DECODER * bool(renorm_decoder),
+                                           float(l1_coefficient),
                                            C.byref(ghost) if ghost is not None else None,
                                            C.byref(out), self.workspace.data_ptr(), self.workspace.numel(), self._stream()),
                 "pv_sae_dense_step")
-        self._inv_norm_key = None
-        self._grad_fresh = False
-        self._sq_fused = False
-        self._grad_sparse = False
+        self._left()
 
     def relu_step(self, x: torch.Tensor, l1_coefficient: float, batch_mean: Optional[torch.Tensor] = None,
                   n_global: Optional[int] = None, update_stats: bool = True, want_out: bool = False,
@@ -397,35 +424,16 @@ class NativeSAE:
         ``dense_step`` (no ghost gradients: those stay with ``dense_step``).  renorm_decoder is deferred as in ``step`` (inverse norms
         now, rows rewritten by ``apply``; a step that goes dense rewrites them itself).  sparse_grads (single process): as in ``step``
         -- only ``grad_sqnorm(from_step=True)`` and ``apply`` may follow (a step that ran dense marks every feature live)."""
-        x = self._check_x(x)
-        self._set_target(x, target)
-        self._ensure_shadows()
-        n = x.shape[0]
-        cap = int(cap if cap is not None else self.relu_cap)
-        key = (self.max_tokens, cap)
-        if getattr(self, "_relu_key", None) != key:
-            need = self.lib.pv_sae_relu_workspace_bytes(self._plan, self.max_tokens, cap)
-            if not need:
-                raise ValueError(f"relu_step: cap must be a multiple of 4 in [4, 256], got {cap}")
-            self._relu_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
-            self._relu_key = key
-        st = self._state()
-        out = N.SaeOut(sae_out=self.sae_out.data_ptr() if want_out else None, topk_idx=None, topk_val=None,
-                       scalars=self.scalars.data_ptr(), fire_count=self.fire_count.data_ptr())
-        bm = self._bm(batch_mean)
-        sp = N.SaeReluSparse(cap=cap, reserved=0, workspace=self._relu_ws.data_ptr(), workspace_bytes=self._relu_ws.numel())
+        x, n, st, out, bm, ng = self._begin(x, target, want_out, batch_mean, n_global, lists=False)
+        cap, self._relu_ws, sp = self._cap_workspace(self._relu_ws, cap, "relu_step", self.lib.pv_sae_relu_workspace_bytes)
         self._relu_last = (n, cap)
-        inv_valid = renorm_decoder and self._inv_norm_key is not None and self._inv_norm_key == self._w_dec_key()
-        N.check(self.lib.pv_sae_relu_step(self._plan, C.byref(st), x.data_ptr(), n, bm.data_ptr() if bm is not None else None,
-                                          int(n_global if n_global is not None else n),
-                                          int(bool(update_stats)) | (2 if renorm_decoder else 0) | (4 if inv_valid else 0) |
-                                          (8 if sparse_grads else 0), float(l1_coefficient), C.byref(sp),
+        N.check(self.lib.pv_sae_relu_step(self._plan, C.byref(st), x.data_ptr(), n, bm.data_ptr() if bm is not None else None, ng,
+                                          N.PV_SAE_UPDATE_STATS * bool(update_stats) | N.PV_SAE_RENORM_DECODER * bool(renorm_decoder) |
+                                          N.PV_SAE_INV_NORM_VALID * self._inv_valid(renorm_decoder) |
+                                          N.PV_SAE_SPARSE_GRADS * bool(sparse_grads), float(l1_coefficient), C.byref(sp),
                                           C.byref(out), self.workspace.data_ptr(), self.workspace.numel(), self._stream()),
                 "pv_sae_relu_step")
-        self._inv_norm_key = None
-        self._grad_fresh = bool(sparse_grads)                     # (the per-feature clip-norm terms exist in that form only)
-        self._sq_fused = False
-        self._grad_sparse = bool(sparse_grads)
+        self._left(fresh=sparse_grads, sparse=sparse_grads)       # (the per-feature clip-norm terms exist in the sparse_grads form only)
 
     def _relu_region(self, name: bytes, dtype: torch.dtype, shape) -> torch.Tensor:
         n, cap = self._relu_last
@@ -457,7 +465,7 @@ class NativeSAE:
         if nd:
             slot[idx.long()] = torch.arange(nd, dtype=torch.int32, device=self.device)
         need = self.lib.pv_sae_ghost_workspace_bytes(self._plan, n, nd)
-        gws = getattr(self, "_ghost_ws", None)
+        gws = self._ghost_ws
         if gws is None or gws.numel() < need:
             self._ghost_ws = gws = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._ghost_keep = (idx, slot)                            # (alive until the kernels have run)
@@ -487,9 +495,7 @@ class NativeSAE:
         ghost = self._ghost_struct(dead_mask, n, ghost_global)
         N.check(self.lib.pv_sae_topk_ghost(self._plan, C.byref(st), x.data_ptr(), n, C.byref(ghost), C.byref(out),
                                            self.workspace.data_ptr(), self.workspace.numel(), self._stream()), "pv_sae_topk_ghost")
-        self._grad_fresh = False                                  # (the per-feature norm terms of the step no longer describe the buffers)
-        self._sq_fused = False
-        self._grad_sparse = False
+        self._left(inv_norm=True)                                 # (the per-feature norm terms of the step no longer describe the buffers)
 
     def gated_step(self, x: torch.Tensor, l1_coefficient: float, batch_mean: Optional[torch.Tensor] = None,
                    n_global: Optional[int] = None, update_stats: bool = True, want_out: bool = False,
@@ -501,25 +507,10 @@ class NativeSAE:
         (pv_sae_gated_step) when a token of the batch holds more -- decided on the GPU (``gated_mode``: 0 sparse, 1 dense), same
         results either way; sparse=False: the dense GEMMs unconditionally."""
         assert self.gated
-        x = self._check_x(x)
-        self._ensure_shadows()                                    # (as in step / dense_step)
-        n = x.shape[0]
-        st = self._state()
-        out = N.SaeOut(sae_out=self.sae_out.data_ptr() if want_out else None, topk_idx=None, topk_val=None,
-                       scalars=self.scalars.data_ptr(), fire_count=self.fire_count.data_ptr())
-        bm = self._bm(batch_mean)
-        flags = int(bool(update_stats)) | 2
-        ng = int(n_global if n_global is not None else n)
+        x, n, st, out, bm, ng = self._begin(x, None, want_out, batch_mean, n_global, lists=False)
+        flags = N.PV_SAE_UPDATE_STATS * bool(update_stats) | N.PV_SAE_RENORM_DECODER
         if sparse:
-            cap = int(cap if cap is not None else self.relu_cap)
-            key = (self.max_tokens, cap)
-            if getattr(self, "_gated_key", None) != key:
-                need = self.lib.pv_sae_gated_sparse_workspace_bytes(self._plan, self.max_tokens, cap)
-                if not need:
-                    raise ValueError(f"gated_step: cap must be a multiple of 4 in [4, 256], got {cap}")
-                self._gated_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
-                self._gated_key = key
-            sp = N.SaeReluSparse(cap=cap, reserved=0, workspace=self._gated_ws.data_ptr(), workspace_bytes=self._gated_ws.numel())
+            cap, self._gated_ws, sp = self._cap_workspace(self._gated_ws, cap, "gated_step", self.lib.pv_sae_gated_sparse_workspace_bytes)
             N.check(self.lib.pv_sae_gated_step_sparse(self._plan, C.byref(st), x.data_ptr(), n, bm.data_ptr() if bm is not None else None,
                                                       ng, flags, float(l1_coefficient), C.byref(sp), C.byref(out),
                                                       self.workspace.data_ptr(), self.workspace.numel(), self._stream()),
@@ -528,31 +519,19 @@ class NativeSAE:
             N.check(self.lib.pv_sae_gated_step(self._plan, C.byref(st), x.data_ptr(), n, bm.data_ptr() if bm is not None else None,
                                                ng, flags, float(l1_coefficient), C.byref(out), self.workspace.data_ptr(),
                                                self.workspace.numel(), self._stream()), "pv_sae_gated_step")
-        self._inv_norm_key = None
-        self._grad_fresh = False
-        self._sq_fused = False
-        self._grad_sparse = False
+        self._left()
 
     def gated_topk_step(self, x: torch.Tensor, batch_mean: Optional[torch.Tensor] = None, n_global: Optional[int] = None,
                         update_stats: bool = True, want_out: bool = False) -> None:
         """One train step of a gated SAE in its top-k form (pv_sae_gated_topk_step): contract as ``gated_step`` (scalars[4] = 0: no L1
         term).  ``topk_idx / topk_val`` rows [0, n) = the magnitude list (feature_acts), rows [n, 2 n) = the gate list."""
         assert self.gated_topk
-        x = self._check_x(x)
-        self._ensure_shadows()
-        n = x.shape[0]
-        st = self._state()
-        out = N.SaeOut(sae_out=self.sae_out.data_ptr() if want_out else None, topk_idx=self.topk_idx.data_ptr(),
-                       topk_val=self.topk_val.data_ptr(), scalars=self.scalars.data_ptr(), fire_count=self.fire_count.data_ptr())
-        bm = self._bm(batch_mean)
-        N.check(self.lib.pv_sae_gated_topk_step(self._plan, C.byref(st), x.data_ptr(), n, bm.data_ptr() if bm is not None else None,
-                                                int(n_global if n_global is not None else n), int(bool(update_stats)) | 2, C.byref(out),
+        x, n, st, out, bm, ng = self._begin(x, None, want_out, batch_mean, n_global, lists=True)
+        N.check(self.lib.pv_sae_gated_topk_step(self._plan, C.byref(st), x.data_ptr(), n, bm.data_ptr() if bm is not None else None, ng,
+                                                N.PV_SAE_UPDATE_STATS * bool(update_stats) | N.PV_SAE_RENORM_DECODER, C.byref(out),
                                                 self.workspace.data_ptr(), self.workspace.numel(), self._gk_scratch.data_ptr(),
                                                 self._gk_scratch.numel(), self._stream()), "pv_sae_gated_topk_step")
-        self._inv_norm_key = None
-        self._grad_fresh = False
-        self._sq_fused = False
-        self._grad_sparse = False
+        self._left()
 
     @property
     def gated_mode(self) -> int:
@@ -560,7 +539,7 @@ class NativeSAE:
         return int(self._gated_ws[:4].view(torch.int32)[0].item())
 
     def _no_pending_sparse(self, what: str) -> None:
-        if getattr(self, "_grad_sparse", False) and self._grad_fresh:
+        if self._grad_sparse and self._grad_fresh:
             raise RuntimeError(f"{what} between a sparse_grads step and its apply(): the step's workspace (the list of live "
                                "features) and its partial gradient buffers are only good for grad_sqnorm(from_step=True) / apply()")
 
@@ -569,7 +548,7 @@ class NativeSAE:
         kernels of the last ``step`` left behind instead of re-reading the 151 MB -- only while the gradient buffers are
         exactly what that step wrote (no all-reduce, no edit through ``g``); otherwise the full pass runs."""
         if from_step and self._grad_fresh:
-            if getattr(self, "_sq_fused", False):                 # (the step's last launch left scalars[3]: PV_SAE_FUSED_SQNORM)
+            if self._sq_fused:                                    # (the step's last launch left scalars[3]: PV_SAE_FUSED_SQNORM)
                 return
             st = self._state()
             N.check(self.lib.pv_sae_grad_sqnorm_step(self._plan, C.byref(st), self.workspace.data_ptr(), self.scalars.data_ptr(),
@@ -594,10 +573,9 @@ class NativeSAE:
                                       float(max_grad_norm) if max_grad_norm else -1.0, float(lr), self.adam_step + 1,
                                       int(j_lo), int(self.d_sae if j_hi is None else j_hi), self._stream()), "pv_sae_apply")
         self.adam_step += 1                                       # (only a call that succeeded is a step)
-        self._grad_fresh = False
-        self._sq_fused = False
-        full = j_lo == 0 and (j_hi is None or j_hi == self.d_sae)
-        self._inv_norm_key = self._w_dec_key() if full else None
+        self._left(sparse=self._grad_sparse)
+        if j_lo == 0 and (j_hi is None or j_hi == self.d_sae):
+            self._inv_norm_key = self._w_dec_key()                # (W_dec as this full-range apply left it: dec_inv_norm is current)
         if self.lazy_w_enc:
             self._w_enc_stale = True
 
@@ -640,9 +618,9 @@ class NativeSAE:
         n = idx.shape[0]
         assert idx.dtype == torch.int32 and val.dtype == torch.float32 and idx.is_contiguous() and val.is_contiguous()
         st = self._state()
-        inv_valid = renorm_decoder and self._inv_norm_key is not None and self._inv_norm_key == self._w_dec_key()
         N.check(self.lib.pv_sae_tp_partial(self._plan, C.byref(st), idx.data_ptr(), val.data_ptr(), n,
-                                           (2 if renorm_decoder else 0) | (4 if inv_valid else 0), self.sae_out.data_ptr(),
+                                           N.PV_SAE_RENORM_DECODER * bool(renorm_decoder) |
+                                           N.PV_SAE_INV_NORM_VALID * self._inv_valid(renorm_decoder), self.sae_out.data_ptr(),
                                            self._stream()), "pv_sae_tp_partial")
         return self.sae_out[:n]
 
@@ -660,11 +638,10 @@ class NativeSAE:
                        fire_count=self.fire_count.data_ptr())
         N.check(self.lib.pv_sae_tp_finish(self._plan, C.byref(st), x.data_ptr(), pre_sum.data_ptr(), idx.data_ptr(), val.data_ptr(),
                                           n, int(n_global if n_global is not None else n),
-                                          int(bool(update_stats)) | (16 if enc_term_only else 0), C.byref(out),
+                                          N.PV_SAE_UPDATE_STATS * bool(update_stats) | N.PV_SAE_TP_ENC_TERM_ONLY * bool(enc_term_only),
+                                          C.byref(out),
                                           self.workspace.data_ptr(), self.workspace.numel(), self._stream()), "pv_sae_tp_finish")
-        self._grad_fresh = False            # (grad_sqnorm(from_step=True) is about pv_sae_step; use grad_sqnorm_rows here)
-        self._sq_fused = False
-        self._grad_sparse = False
+        self._left(inv_norm=True)           # (grad_sqnorm(from_step=True) is about pv_sae_step; use grad_sqnorm_rows here)
 
     # the feature-parallel step's glue (sae/feature_parallel.py): exchange buffers the kernels write in place
     def tp_bind(self, pack: torch.Tensor, bucket: torch.Tensor, lo: int, d_sae_total: int) -> None:

@@ -6,11 +6,12 @@ eval_dataset=None)``, ``train_step`` argument names and 7-tuple, ``run() -> sae`
 operations inside a step is the reference's (:278-411): renorm decoder -> zero_grad -> forward ->
 firing statistics -> backward -> clip_grad_norm_ -> remove parallel gradient -> Adam -> scheduler.
 
-On an MI355X (fp32 standard SAE with layer_norm / no input normalisation, no ghost grads) the step runs on
-``NativeSAE`` (HIP kernels) directly on the module's parameter storage -- the k-sparse step for top-k, the
-dense fused step (exact fp32 MFMA GEMMs with ReLU / L1 / loss / gate epilogues) for ReLU + L1, ghost gradients
-included; Adam moments live in the engine.  Everything else (gated, transcoder, tanh-relu, top-k with ghost grads,
-CPU) takes the PyTorch path below, which is the reference algorithm verbatim.
+On an MI355X the step runs on ``NativeSAE`` (HIP kernels) directly on the module's parameter storage; Adam moments
+live in the engine.  ``train_step`` resolves the route once (``_native_kind``: "topk" / "relu" / "gated", under the
+conditions listed in ``_native_limits``) and ``_native_step`` takes it: ``_step_topk`` (the k-sparse step, also a
+top-k Transcoder, ghost gradients included), ``_step_dense`` (ReLU + L1 and the gated SAE), ``_step_feature_parallel``.
+Everything else (other activations, widths beyond the limits, CPU) takes the PyTorch path below, which is the
+reference algorithm verbatim; on a GPU the trainer says once which condition sent it there (``_native_why_not``).
 
 Data parallel (new functionality, SURVEY.md section 8e -- the reference is single-process): one process
 per GPU, each with its share of the global token batch and a 1/W shard of the OPTIMIZER, by feature
@@ -48,6 +49,19 @@ def _wandb():
         return wandb
     except Exception:
         return None
+
+
+# The numeric limits of the fused HIP steps and the sentences that state them (VisionSAETrainer._native_limits): every width a
+# multiple of _MULT, of _MULT_DENSE on the dense GEMMs and in the ghost term; the {}-fields are filled by _native_why_not.
+_MULT, _MULT_DENSE, _MAX_D_IN, _MAX_D_SAE, _MAX_K = 4, 8, 1280, 65536, 256
+_D_IN = f"d_in = {{cfg.d_in}} (supported: multiples of {_MULT} up to {_MAX_D_IN} = ViT-H/14)"
+_D_SAE = f"d_sae = {{cfg.d_sae}} (supported: multiples of {_MULT} up to {_MAX_D_SAE})"
+_K = f"k = {{k}} (supported: 1..{_MAX_K})"
+_TC_WIDTHS = (f"a transcoder with d_out != d_in and the skip connection / widths that are not multiples of {_MULT_DENSE} / "
+              f"d_out > {_MAX_D_IN}")
+_DENSE_WIDTHS = f"d_in = {{cfg.d_in}}, d_sae = {{cfg.d_sae}} (the ReLU + L1 and the gated steps: multiples of {_MULT_DENSE})"
+_GHOST_WIDTH = f"ghost gradients with d_in = {{cfg.d_in}} (supported: multiples of {_MULT_DENSE})"
+_NOT_AN_SAE = "a {kind} (supported: StandardSparseAutoencoder, GatedSparseAutoencoder, a Transcoder under cfg.is_transcoder)"
 
 
 class VisionSAETrainer:
@@ -91,6 +105,9 @@ class VisionSAETrainer:
         self._force_dist = False                            # see _mr
         self._fp = None                                     # FeatureParallelSAE (this rank's shard engine + choreography)
         self._fp_dirty = False                              # the module's parameters lag behind the shards
+        self._fp_drop = False                               # use_feature_parallel(drop_replicas=True)
+        self._target = None                                 # transcoder: the target activation of the current step
+        self._warned_torch_path = False
 
     @property
     def _mr(self) -> bool:
@@ -195,76 +212,65 @@ class VisionSAETrainer:
         return medians
 
     # ---- native engine ----------------------------------------------------------------------------
-    def _native_kind(self, sae, x: torch.Tensor) -> Optional[str]:
-        """Which fused HIP step serves this SAE: "topk" (k-sparse step, sae.hip), "relu" (dense ReLU + L1 step,
-        sae_dense.hip), "gated" (the gated SAE's step: sparse where the batch allows it, sae_gated.hip) or None (PyTorch path: the top-k
-        gated form / other activations / d_out != d_in / CPU)."""
+    def _native_limits(self, sae, x: Optional[torch.Tensor] = None):
+        """(kind, [(holds, text), ...]): the fused HIP step that would serve this SAE -- "topk" (k-sparse step, pv_sae_step; also the
+        top-k Transcoder), "relu" (ReLU / tanh-relu + L1: pv_sae_relu_step, sparse where the batch allows it, pv_sae_dense_step with
+        ghost gradients), "gated" (a GatedSparseAutoencoder: pv_sae_gated_step_sparse, or pv_sae_gated_topk_step for its top-k form), None
+        for any other activation -- and EVERY condition it runs under, each with the sentence that tells the user about it (its {}-fields
+        are filled by ``_native_why_not``).  The one statement of these limits: ``_native_kind`` takes the step when all hold,
+        ``_native_why_not`` lists those that do not.  The last entry is the only one that needs the GPU."""
+        from .variants import GatedSparseAutoencoder, Transcoder
         cfg = sae.cfg
-        from .variants import Transcoder
-        # a Transcoder (sae/transcoder.py) of equal input and output width runs on the same two steps (pv_sae_transcoder):
-        # no ghost gradients; with a process group the tokens are sharded and the optimizer replicated (one all-reduce of the flat
-        # gradient buffer: _native_dense_step for ReLU, _native_dp_step's transcoder branch for top-k)
-        # ... and one between hook points of DIFFERENT width (no skip connection: the reference's needs d_out == d_in) on the same steps with
-        # every row padded to the wider of the two (pv_sae_transcoder.d_in_true / d_out_true)
-        d_out = int(getattr(cfg, "d_out", cfg.d_in))
-        # ghost gradients on a transcoder (round 6; transcoder.py:82-86: the ghost term sees the INPUT activation): equal widths, one process
-        tc_ghost_ok = not cfg.use_ghost_grads or (d_out == int(cfg.d_in) and not self._mr and cfg.d_in % 8 == 0)
-        is_tc = (isinstance(sae, Transcoder) and tc_ghost_ok and getattr(self, "_target", None) is not None
-                 and (d_out == int(cfg.d_in) or (sae._parameters.get("W_skip") is None and d_out % 8 == 0 and d_out <= 1280
-                                                 and cfg.d_in % 8 == 0)))
-        from .variants import GatedSparseAutoencoder
-        # a GatedSparseAutoencoder (sae.py:648-792) with the ReLU magnitude path has its own step (pv_sae_gated_step_sparse: the open gates
-        # as per-token lists where the batch allows it, the dense GEMMs of pv_sae_gated_step otherwise -- decided on the GPU)
-        # ... and the top-k form (TopK on the magnitudes and on the gate activations) its own k-sparse step (pv_sae_gated_topk_step)
-        is_gated = (isinstance(sae, GatedSparseAutoencoder) and cfg.d_in % 8 == 0 and cfg.d_sae % 8 == 0
-                    and (cfg.activation_fn_str == "relu"
-                         or (cfg.activation_fn_str == "topk" and 1 <= cfg.activation_fn_kwargs.get("k", 0) <= 256)))
-        common = (x.is_cuda and (isinstance(sae, StandardSparseAutoencoder) or is_tc or is_gated) and cfg.dtype == torch.float32
-                  and cfg.normalize_activations in ("layer_norm", "constant_norm_rescale", "none", None)
-                  and all(p.is_cuda and p.dtype == torch.float32 for p in sae._parameters.values() if p is not None)   # (not .parameters(): no sync of lazily kept layouts)
-                  and cfg.d_in % 4 == 0 and cfg.d_in <= 1280 and cfg.d_sae % 4 == 0 and cfg.d_sae <= 65536
-                  and self._native_pref is not False)
-        if not common:
+        act, k, d_in, d_sae = cfg.activation_fn_str, cfg.activation_fn_kwargs.get("k", 0), int(cfg.d_in), int(cfg.d_sae)
+        d_out = int(getattr(cfg, "d_out", d_in))
+        gated, tc, ghost = isinstance(sae, GatedSparseAutoencoder), isinstance(sae, Transcoder), bool(cfg.use_ghost_grads)
+        kind = None if act not in (("relu", "topk") if gated else ("topk", "relu", "tanh-relu")) else \
+            "gated" if gated else "topk" if act == "topk" else "relu"
+        return kind, [
+            # a Transcoder runs on the same steps (pv_sae_transcoder) once train_step has split its target off the batch
+            (isinstance(sae, StandardSparseAutoencoder) or gated or (tc and self._target is not None), _NOT_AN_SAE),
+            (cfg.dtype == torch.float32, "dtype {cfg.dtype} (the fused steps keep fp32 master weights)"),
+            (d_in <= _MAX_D_IN and d_in % _MULT == 0, _D_IN),
+            (d_sae <= _MAX_D_SAE and d_sae % _MULT == 0, _D_SAE),
+            (act != "topk" or 1 <= k <= _MAX_K, _K),
+            # ghost gradients on a transcoder (transcoder.py:82-86: the ghost term sees the INPUT activation): equal widths, one process
+            (not (tc and ghost) or (d_out == d_in and not self._mr),
+             "ghost gradients on a transcoder with tokens sharded over ranks / d_out != d_in"),
+            (kind is not None, "activation {cfg.activation_fn_str!r}"),
+            # lp_norm > 1 in the sparsity term (sae.py:617) runs on the dense GEMMs' epilogues
+            (kind != "relu" or float(getattr(sae, "lp_norm", 1)) >= 1.0,
+             "lp_norm = {sae.lp_norm} (p < 1 has no finite gradient at zero activations: supported p >= 1)"),
+            # hook points of DIFFERENT width: every row padded to the wider of the two (pv_sae_transcoder.d_in_true / d_out_true); the
+            # reference's skip connection needs d_out == d_in
+            (not tc or d_out == d_in or (sae._parameters.get("W_skip") is None and d_out % _MULT_DENSE == 0 and d_out <= _MAX_D_IN
+                                         and d_in % _MULT_DENSE == 0), _TC_WIDTHS),
+            (cfg.normalize_activations in ("layer_norm", "constant_norm_rescale", "none", None),
+             "normalize_activations = {cfg.normalize_activations!r}"),
+            (not (gated or kind == "relu") or (d_in % _MULT_DENSE == 0 and d_sae % _MULT_DENSE == 0), _DENSE_WIDTHS),
+            (not ghost or d_in % _MULT_DENSE == 0, _GHOST_WIDTH),         # (pv_sae_topk_ghost, the ghost GEMMs of pv_sae_dense_step)
+            (self._on_device(sae, x), "a parameter is not a contiguous fp32 CUDA tensor"),
+        ]
+
+    @staticmethod
+    def _on_device(sae, x: Optional[torch.Tensor]) -> bool:
+        """The device entry of ``_native_limits``: the step's input (when given) and every parameter on the GPU, in fp32."""
+        return (x is None or x.is_cuda) and all(p.is_cuda and p.dtype == torch.float32       # (not .parameters(): no sync of lazily kept layouts)
+                                                for p in sae._parameters.values() if p is not None)
+
+    def _native_kind(self, sae, x: torch.Tensor) -> Optional[str]:
+        """Which fused HIP step serves this SAE ("topk" / "relu" / "gated", see ``_native_limits``), or None: the PyTorch path."""
+        if self._native_pref is False:
             return None
-        if is_gated:
-            return "gated"
-        if (cfg.activation_fn_str == "topk" and 1 <= cfg.activation_fn_kwargs.get("k", 0) <= 256
-                # ghost gradients on top-k (pv_sae_topk_ghost): plain SAE, d_in a multiple of 8
-                and (not cfg.use_ghost_grads or cfg.d_in % 8 == 0)):
-            return "topk"
-        # ReLU + L1; since round 6 also "tanh-relu" (sae.py:823-830) and lp_norm > 1 in the sparsity term (sae.py:617) -- both on the dense
-        # GEMMs' epilogues (the sparse form of the step serves the plain one)
-        if (cfg.activation_fn_str in ("relu", "tanh-relu") and float(getattr(sae, "lp_norm", 1)) >= 1.0
-                and cfg.d_in % 8 == 0 and cfg.d_sae % 8 == 0):
-            return "relu"
-        return None
+        kind, limits = self._native_limits(sae, x)
+        return kind if all(holds for holds, _ in limits) else None
 
     def _native_ok(self, sae, x: torch.Tensor) -> bool:
         return self._native_kind(sae, x) is not None
 
     def _native_why_not(self, sae) -> str:
-        """Best-effort diagnosis for the one-time fallback warning (the limits of ``_native_kind``)."""
-        cfg = sae.cfg
-        why = []
-        if cfg.dtype != torch.float32:
-            why.append(f"dtype {cfg.dtype} (the fused steps keep fp32 master weights)")
-        if cfg.d_in > 1280 or cfg.d_in % 4:
-            why.append(f"d_in = {cfg.d_in} (supported: multiples of 4 up to 1280 = ViT-H/14)")
-        if cfg.d_sae > 65536 or cfg.d_sae % 4:
-            why.append(f"d_sae = {cfg.d_sae} (supported: multiples of 4 up to 65536)")
-        if cfg.activation_fn_str == "topk" and not 1 <= cfg.activation_fn_kwargs.get("k", 0) <= 256:
-            why.append(f"k = {cfg.activation_fn_kwargs.get('k')} (supported: 1..256)")
-        if getattr(cfg, "is_transcoder", False) and cfg.use_ghost_grads and (self._mr or int(getattr(cfg, "d_out", cfg.d_in)) != int(cfg.d_in)):
-            why.append("ghost gradients on a transcoder with tokens sharded over ranks / d_out != d_in")
-        if cfg.activation_fn_str not in ("topk", "relu", "tanh-relu"):
-            why.append(f"activation {cfg.activation_fn_str!r}")
-        if float(getattr(sae, "lp_norm", 1)) < 1.0:
-            why.append(f"lp_norm = {sae.lp_norm} (p < 1 has no finite gradient at zero activations: supported p >= 1)")
-        if getattr(cfg, "is_transcoder", False) and int(getattr(cfg, "d_out", cfg.d_in)) != int(cfg.d_in):
-            why.append("a transcoder with d_out != d_in and the skip connection / widths that are not multiples of 8 / d_out > 1280")
-        if cfg.normalize_activations not in ("layer_norm", "constant_norm_rescale", "none", None):
-            why.append(f"normalize_activations = {cfg.normalize_activations!r}")
-        return "; ".join(why) or "a parameter is not a contiguous fp32 CUDA tensor"
+        """The one-time fallback warning's diagnosis: the conditions of ``_native_limits`` that do not hold."""
+        return "; ".join(text.format(cfg=sae.cfg, sae=sae, k=sae.cfg.activation_fn_kwargs.get("k"), kind=type(sae).__name__)
+                         for holds, text in self._native_limits(sae)[1] if not holds)
 
     def _get_engine(self, sae, n_tokens: int):
         from .native_sae import NativeSAE
@@ -403,20 +409,21 @@ class VisionSAETrainer:
             act_freq_scores = torch.zeros(hp.d_sae, device=hp.device)
             n_frac_active_tokens = 0
 
-        native = self._native_ok(sparse_autoencoder, sae_in)
+        kind = self._native_kind(sparse_autoencoder, sae_in)                     # the route, resolved here and nowhere below
+        native = kind is not None
         if self._native_pref is True and not native:
             from .._native import NativeError
             raise NativeError("use_native(True): this SAE configuration / input is not served by the fused HIP step "
                               f"(activation {hp.activation_fn_str!r}, architecture {getattr(hp, 'architecture', 'standard')!r}, "
                               f"device {sae_in.device})")
-        if not native and sae_in.is_cuda and self._native_pref is None and not getattr(self, "_warned_torch_path", False):
+        if not native and sae_in.is_cuda and self._native_pref is None and not self._warned_torch_path:
             # auto mode on a GPU: say ONCE why this run is not on the fused kernels (a silent PyTorch path is ~1000 x slower)
             self._warned_torch_path = True
             import warnings
             warnings.warn("vit_prisma_amd: VisionSAETrainer trains this SAE on the PyTorch path, not on the MI355X kernels: "
                           + self._native_why_not(sparse_autoencoder), stacklevel=2)
         if native:
-            loss, mse_loss, l1_loss, l0 = self._native_step(sparse_autoencoder, optimizer, scheduler, sae_in,
+            loss, mse_loss, l1_loss, l0 = self._native_step(kind, sparse_autoencoder, optimizer, scheduler, sae_in,
                                                             act_freq_scores, n_forward_passes_since_fired)
         else:
             loss, mse_loss, l1_loss, l0 = self._torch_step(sparse_autoencoder, optimizer, scheduler, sae_in,
@@ -425,114 +432,170 @@ class VisionSAETrainer:
         self.last_step_native = native
         return loss, mse_loss, l1_loss, l0, act_freq_scores, n_forward_passes_since_fired, n_frac_active_tokens
 
-    def _native_step(self, sae, optimizer, scheduler, x, act_freq_scores, n_since_fired):
+    def _native_step(self, kind, sae, optimizer, scheduler, x, act_freq_scores, n_since_fired):
+        """One step on the HIP kernels.  kind ("topk" / "relu" / "gated", from ``train_step``) picks the route: ``_step_feature_parallel``
+        (multi-rank top-k of a plain SAE without ghost gradients, unless ``use_feature_parallel(False)``), ``_step_topk`` or
+        ``_step_dense``; the routes differ in what lies between here and the epilogue, which is common."""
         lr = optimizer.param_groups[0]["lr"]
-        kind = self._native_kind(sae, x)
-        if kind in ("relu", "gated"):
-            return self._native_dense_step(sae, optimizer, scheduler, x, lr, act_freq_scores, n_since_fired, gated=kind == "gated")
-        ghost_mr = bool(sae.cfg.use_ghost_grads) and sae.training
-        if self._use_tp(sae) and not self.is_transcoder and not ghost_mr:      # (the feature-parallel step serves the plain SAE, no ghost term)
-            return self._native_tp_step(sae, optimizer, scheduler, x, lr, act_freq_scores, n_since_fired)
-        self._dp_flush()                                        # parameters of the previous step must have landed
-        eng = self._get_engine(sae, x.shape[0])
-        # statistics tensors are the caller's: the kernels update them in place
-        eng.act_freq_scores = act_freq_scores
-        eng.n_fwd_since_fired = n_since_fired
         ghost = bool(sae.cfg.use_ghost_grads) and sae.training
-        if not self._mr and ghost:
-            # top-k + ghost gradients (sae.py:151-179; the mask of train_sae.py:330-332 is taken BEFORE this step's statistics): the
-            # k-sparse step with complete gradient buffers over a decoder renormalised in place, then the ghost term's additions
-            dead = n_since_fired > sae.cfg.dead_feature_window
-            eng.renorm_decoder()
-            eng.step(x, update_stats=True, renorm_decoder=False, sparse_grads=False, want_out=True,
-                     target=self._target if eng.transcoder else None)
-            eng.topk_ghost(x, dead)
-            eng.grad_sqnorm()
-            eng.apply(lr, self.cfg.max_grad_norm)
-        elif not self._mr:
-            # set_decoder_norm_to_unit_norm is part of the step; one process = nobody but the step's own apply reads the
-            # gradient buffers, so the rows of features that kept no token are neither zeroed nor read (PV_SAE_SPARSE_GRADS)
-            eng.step(x, update_stats=True, renorm_decoder=True, sparse_grads=True, target=self._target if eng.transcoder else None,
-                     fused_sqnorm=True)
-            eng.grad_sqnorm(from_step=True)                     # clip_grad_norm_ (the gradient is as the step wrote it)
-            eng.apply(lr, self.cfg.max_grad_norm)
+        fp = kind == "topk" and self._use_tp(sae) and not self.is_transcoder and not ghost
+        if fp:
+            out = self._step_feature_parallel(sae, x, lr, act_freq_scores, n_since_fired)
         else:
-            self._native_dp_step(eng, sae, x, lr, act_freq_scores, n_since_fired)
+            self._dp_flush()                                    # parameters of the previous step must have landed
+            eng = self._get_engine(sae, x.shape[0])
+            # statistics tensors are the caller's: the kernels update them in place
+            eng.act_freq_scores = act_freq_scores
+            eng.n_fwd_since_fired = n_since_fired
+            # train_sae.py:330-332: the mask of the ghost term is taken BEFORE this step's statistics
+            # (none for a gated SAE; none for a transcoder with its tokens sharded, which _native_limits keeps off these steps)
+            dead = None
+            if ghost and kind != "gated" and not (self._mr and self.is_transcoder):
+                dead = n_since_fired > sae.cfg.dead_feature_window
+            if kind == "topk":
+                self._step_topk(eng, x, lr, dead, act_freq_scores, n_since_fired)
+            else:
+                self._step_dense(eng, kind == "gated", float(sae.l1_coefficient), x, lr, dead, act_freq_scores, n_since_fired)
         optimizer._opt_called = True                            # the native apply IS the optimizer step
         scheduler.step()
+        if fp:
+            return out
         self._invalidate_inference_engine(sae)
         sc = eng.scalars.clone()
-        return sc[0], sc[1], None, sc[2]
+        return sc[0], sc[1], None if kind == "topk" else sc[4], sc[2]
 
-    def _native_dense_step(self, sae, optimizer, scheduler, x, lr, act_freq_scores, n_since_fired, gated: bool = False):
-        """ReLU + L1 (sae.py:617-626; also a ReLU Transcoder) on pv_sae_relu_step / pv_sae_dense_step, or a Gated SAE on
-        pv_sae_gated_step_sparse.  Multi-rank: tokens sharded, ONE all-reduce of the flat gradient buffer and a replicated optimizer (the
-        step is 6-11 ms of fp32 GEMMs: the 151 MB are not what bounds it), statistics and losses over the global batch like every
-        other path."""
-        self._dp_flush()
-        eng = self._get_engine(sae, x.shape[0])
-        eng.act_freq_scores = act_freq_scores
-        eng.n_fwd_since_fired = n_since_fired
-        l1 = float(sae.l1_coefficient)
-        target = self._target if eng.transcoder else None
+    # ---- the pieces of a multi-rank step -----------------------------------------------------------
+    def _global_mean(self, t: torch.Tensor, n_global: int) -> torch.Tensor:
+        """Mean over the GLOBAL batch of what the loss is taken against (its normaliser, sae.py:145; a transcoder: the target's)."""
+        import torch.distributed as dist
+        bm = t.float().sum(dim=0)
+        dist.all_reduce(bm)
+        return bm / n_global
 
-        def run(**kw):
-            if gated and getattr(eng, "gated_topk", False):
-                eng.gated_topk_step(x, **kw)
-            elif gated:
-                eng.gated_step(x, l1, **kw)
-            elif kw.get("dead_mask") is not None:                 # ghost gradients: exp(hidden_pre) of the dead columns is a dense quantity
-                eng.dense_step(x, l1, renorm_decoder=True, target=target, **kw)
-            else:
-                # sparse where the batch allows it, the dense GEMMs otherwise: the GPU decides (NativeSAE.relu_step)
-                kw.pop("dead_mask", None)
-                eng.relu_step(x, l1, renorm_decoder=True, target=target, sparse_grads=not self._mr, **kw)
+    @staticmethod
+    def _ghost_global(eng, x: torch.Tensor, n_global: int):
+        """``ghost_global`` of NativeSAE.topk_ghost / dense_step after a pass that left ``sae_out`` and the mse loss of this rank's tokens:
+        the ghost term (sae.py:151-179) normalises by the residual's column mean and rescales by the mse loss of the WHOLE batch."""
+        import torch.distributed as dist
+        gl = torch.cat([(eng.sae_out[:x.shape[0]] - x).sum(dim=0), eng.scalars[1:2]])
+        dist.all_reduce(gl)
+        return gl[:eng.d_in] / n_global, gl[eng.d_in:], n_global
 
+    def _pack_bucket(self, eng, n_scalars: int, gb_dec: bool):
+        """The step's small bucket, filled: [gb_dec (d_in) |] fire counts (d_sae) | scalars[:n_scalars] (loss, mse, l0; the dense forms
+        also -, l1, ghost, aux).  Packed BEFORE the gradient collective is issued, reduced after it (``_reduce_bucket``)."""
+        lead, d_sae = eng.d_in if gb_dec else 0, eng.d_sae
+        if self._small is None or self._small.numel() != lead + d_sae + n_scalars:
+            self._small = torch.empty(lead + d_sae + n_scalars, dtype=torch.float32, device=eng.scalars.device)
+        small = self._small
+        if gb_dec:
+            small[:lead].copy_(eng._g["b_dec"])
+        small[lead:lead + d_sae].copy_(eng.fire_count)
+        small[lead + d_sae:].copy_(eng.scalars[:n_scalars])
+        return small, lead
+
+    def _reduce_bucket(self, eng, bucket, act_freq_scores, n_since_fired) -> None:
+        """One all-reduce of the packed bucket, then its parts go back where they came from: statistics and losses over the global batch."""
+        import torch.distributed as dist
+        small, lead = bucket
+        dist.all_reduce(small)
+        if lead:
+            eng._g["b_dec"].copy_(small[:lead])
+        n_scalars = small.numel() - lead - eng.d_sae
+        eng.scalars[:n_scalars].copy_(small[lead + eng.d_sae:])
+        eng.scalars[2] /= self.world                            # l0 is a mean over tokens
+        self._count_firing(small[lead:lead + eng.d_sae], act_freq_scores, n_since_fired)
+
+    @staticmethod
+    def _count_firing(fire: torch.Tensor, act_freq_scores, n_since_fired) -> None:
+        """train_sae.py:356-361 on the global batch (one process: the kernels do it, PV_SAE_UPDATE_STATS)."""
+        n_since_fired += 1
+        n_since_fired[fire > 0] = 0
+        act_freq_scores += fire
+
+    # ---- the routes ----------------------------------------------------------------------------------
+    def _step_topk(self, eng, x, lr, dead, act_freq_scores, n_since_fired) -> None:
+        """The k-sparse step (pv_sae_step) of a plain SAE or a Transcoder; dead: the ghost term's mask (pv_sae_topk_ghost) or None.
+        Multi-rank: tokens sharded; the gradient rows reduce-scattered to the ranks that own them (module docstring), or -- a Transcoder
+        (b_dec_out, W_skip beside the four tensors the row shards know), a d_sae that does not shard -- all-reduced for a replicated
+        optimizer."""
+        tgt = {"target": self._target} if eng.transcoder else {}
         if not self._mr:
-            dead = None
-            if sae.cfg.use_ghost_grads and sae.training and not gated:        # train_sae.py:330-332 (the mask is taken BEFORE this step's statistics)
-                dead = n_since_fired > sae.cfg.dead_feature_window
-            run(update_stats=True, **({} if gated else {"dead_mask": dead}))
-        else:
-            import torch.distributed as dist
-            W = self.world
-            n_global = x.shape[0] * W
-            bm = (target if target is not None else x).float().sum(dim=0)
-            dist.all_reduce(bm)                                 # global batch mean of what the loss is taken against (sae.py:145)
-            if sae.cfg.use_ghost_grads and sae.training and not gated and not eng.transcoder:
-                # ghost gradients (sae.py:151-179) need the residual's column mean and the mse loss of the WHOLE batch before the ghost
-                # term is formed: a pass without it gives this rank's share of both (one small all-reduce), the step proper follows
-                dead = n_since_fired > sae.cfg.dead_feature_window
-                eng.dense_step(x, l1, batch_mean=bm / n_global, n_global=n_global, update_stats=False, want_out=True, renorm_decoder=True)
-                gl = torch.cat([(eng.sae_out[:x.shape[0]] - x).sum(dim=0), eng.scalars[1:2]])
-                dist.all_reduce(gl)
-                d_in_ = eng.d_in
-                eng.dense_step(x, l1, batch_mean=bm / n_global, n_global=n_global, update_stats=False, renorm_decoder=True,
-                               dead_mask=dead, ghost_global=(gl[:d_in_] / n_global, gl[d_in_:], n_global))
+            if dead is not None:
+                # sae.py:151-179: the step with complete gradient buffers over a decoder renormalised in place (the ghost term reads
+                # W_dec as it lies), then the ghost term's additions
+                eng.renorm_decoder()
+                eng.step(x, update_stats=True, renorm_decoder=False, sparse_grads=False, want_out=True, **tgt)
+                eng.topk_ghost(x, dead)
+                eng.grad_sqnorm()
             else:
-                run(batch_mean=bm / n_global, n_global=n_global, update_stats=False)
-            d_sae = eng.d_sae
-            if self._small is None or self._small.numel() != d_sae + 7:
-                self._small = torch.empty(d_sae + 7, dtype=torch.float32, device=x.device)
-            small = self._small
-            small[:d_sae].copy_(eng.fire_count)
-            small[d_sae:].copy_(eng.scalars[:7])
+                # set_decoder_norm_to_unit_norm is part of the step; one process = nobody but the step's own apply reads the
+                # gradient buffers, so the rows of features that kept no token are neither zeroed nor read (PV_SAE_SPARSE_GRADS)
+                eng.step(x, update_stats=True, renorm_decoder=True, sparse_grads=True, fused_sqnorm=True, **tgt)
+                eng.grad_sqnorm(from_step=True)                 # clip_grad_norm_ (the gradient is as the step wrote it)
+            eng.apply(lr, self.cfg.max_grad_norm)
+            return
+        import torch.distributed as dist
+        n_global = x.shape[0] * self.world
+        dp = dict(batch_mean=self._global_mean(self._target if eng.transcoder else x, n_global), n_global=n_global, update_stats=False)
+        if dead is not None:
+            eng.renorm_decoder()
+            eng.step(x, renorm_decoder=False, want_out=True, **dp)
+            eng.topk_ghost(x, dead, ghost_global=self._ghost_global(eng, x, n_global))
+        else:
+            eng.step(x, renorm_decoder=True, **dp, **tgt)
+        shard = None if eng.transcoder else self._shard(eng.d_sae)
+        bucket = self._pack_bucket(eng, 3, gb_dec=not eng.transcoder)
+        if eng.transcoder:
+            dist.all_reduce(eng.flat_g)
+        elif shard is None:
+            dist.all_reduce(eng.flat_g[:eng.n_flat - eng.d_in])  # replicated optimizer: every rank needs every row (gb_dec: the bucket)
+        else:
+            for name in ("W_encT", "W_dec", "b_enc"):
+                self._reduce_scatter_rows(dist, eng._g[name], *shard)
+        self._reduce_bucket(eng, bucket, act_freq_scores, n_since_fired)
+        if shard is None:
+            eng.grad_sqnorm()
+            eng.apply(lr, self.cfg.max_grad_norm)
+            return
+        j_lo, j_hi = shard
+        eng.grad_sqnorm_rows(j_lo, j_hi, include_b_dec=self.rank == 0)
+        dist.all_reduce(eng.scalars[3:4])                       # the clip norm is over the GLOBAL gradient
+        eng.apply(lr, self.cfg.max_grad_norm, j_lo, j_hi)       # this rank's rows (+ b_dec, identically everywhere)
+        self._pending = [dist.all_gather_into_tensor(full, full[j_lo:j_hi], async_op=True)
+                         for full in (eng.W_encT, eng.params["W_dec"], eng.params["b_enc"])]
+
+    def _step_dense(self, eng, gated: bool, l1: float, x, lr, dead, act_freq_scores, n_since_fired) -> None:
+        """ReLU + L1 (sae.py:617-626; also a ReLU Transcoder) on pv_sae_relu_step -- sparse where the batch allows it, the dense GEMMs
+        otherwise: the GPU decides -- or pv_sae_dense_step (ghost gradients: exp(hidden_pre) of the dead columns is a dense quantity),
+        or a Gated SAE on its own step.  Multi-rank: tokens sharded, ONE all-reduce of the flat gradient buffer and a replicated
+        optimizer (the step is 6-11 ms of fp32 GEMMs: the 151 MB are not what bounds it), statistics and losses over the global batch
+        like every other route."""
+        tgt = {"target": self._target} if eng.transcoder else {}
+        dp = dict(update_stats=True)
+        if self._mr:
+            import torch.distributed as dist
+            n_global = x.shape[0] * self.world
+            dp = dict(batch_mean=self._global_mean(self._target if eng.transcoder else x, n_global), n_global=n_global, update_stats=False)
+        if gated and eng.gated_topk:
+            eng.gated_topk_step(x, **dp)
+        elif gated:
+            eng.gated_step(x, l1, **dp)
+        elif dead is not None:
+            if self._mr:
+                # the ghost term's two batch-wide quantities: a pass without it gives this rank's share of both, the step proper follows
+                eng.dense_step(x, l1, want_out=True, renorm_decoder=True, **dp)
+                dp["ghost_global"] = self._ghost_global(eng, x, n_global)
+            eng.dense_step(x, l1, renorm_decoder=True, dead_mask=dead, **dp, **tgt)
+        else:
+            eng.relu_step(x, l1, renorm_decoder=True, sparse_grads=not self._mr, **dp, **tgt)
+        if self._mr:
+            bucket = self._pack_bucket(eng, 7, gb_dec=False)
             dist.all_reduce(eng.flat_g)                         # every rank's share of the gradient (scaled by 1 / N_global already)
-            dist.all_reduce(small)                              # fire counts | loss, mse, l0, -, l1, ghost, aux in one bucket
-            fire = small[:d_sae]
-            eng.scalars[:7].copy_(small[d_sae:])
-            eng.scalars[2] /= W                                 # l0 is a mean over tokens
-            n_since_fired += 1                                  # train_sae.py:356-361 on the global batch
-            n_since_fired[fire > 0] = 0
-            act_freq_scores += fire
-        # clip_grad_norm_ over the whole (summed) gradient; single-process relu_step: from the per-feature terms the step left
+            self._reduce_bucket(eng, bucket, act_freq_scores, n_since_fired)
+        # clip_grad_norm_ over the whole (summed) gradient; one process: from the per-feature terms the step left
         eng.grad_sqnorm(from_step=not self._mr)
         eng.apply(lr, self.cfg.max_grad_norm)
-        optimizer._opt_called = True
-        scheduler.step()
-        self._invalidate_inference_engine(sae)
-        sc = eng.scalars.clone()
-        return sc[0], sc[1], sc[4], sc[2]
 
     @staticmethod
     def _invalidate_inference_engine(sae) -> None:
@@ -548,7 +611,7 @@ class VisionSAETrainer:
         k, ln = sae.cfg.activation_fn_kwargs["k"], sae.cfg.normalize_activations
         return lambda We, Wd, be, bd: NativeSAE(We, Wd, be, bd, k=k, layer_norm=ln, max_tokens=max_tokens)
 
-    def _native_tp_step(self, sae, optimizer, scheduler, x, lr, act_freq_scores, n_since_fired):
+    def _step_feature_parallel(self, sae, x, lr, act_freq_scores, n_since_fired):
         """Feature-parallel step (sae/feature_parallel.py): every rank brings its tokens, all ranks see the global batch,
         each owns d_sae / world features for good."""
         import torch.distributed as dist
@@ -561,92 +624,15 @@ class VisionSAETrainer:
                                           sae.cfg.activation_fn_kwargs["k"], self._make_shard_engine(sae, n_global),
                                           dist=dist, rank=self.rank, world=self.world)
         fp = self._fp
-        if getattr(self, "_fp_drop", False):                    # the shards are the truth from here on: release the replicas
+        if self._fp_drop:                                       # the shards are the truth from here on: release the replicas
             for n in ("W_enc", "W_dec"):
                 p = getattr(sae, n)
                 if p.numel():
                     p.data = torch.empty(0, dtype=p.dtype, device=p.device)
         loss, l0 = fp.step(fp.gather_tokens(x), lr, self.cfg.max_grad_norm)
         self._fp_dirty = True
-        n_since_fired += 1                                      # train_sae.py:356-361 on the global batch
-        n_since_fired[fp.fire_count > 0] = 0
-        act_freq_scores += fp.fire_count
-        optimizer._opt_called = True
-        scheduler.step()
+        self._count_firing(fp.fire_count, act_freq_scores, n_since_fired)
         return loss, loss, None, l0
-
-    def _native_dp_step(self, eng, sae, x, lr, act_freq_scores, n_since_fired):
-        import torch.distributed as dist
-        W = self.world
-        n_global = x.shape[0] * W
-        d_in, d_sae = eng.d_in, eng.d_sae
-        if eng.transcoder:
-            # a top-k Transcoder (b_dec_out, W_skip beside the four tensors the row shards know): tokens sharded, the mean of the
-            # TARGET all-reduced (its loss normaliser, transcoder.py:78), ONE all-reduce of the whole flat gradient buffer and a
-            # replicated optimizer, as the dense step's multi-rank form
-            bm = self._target.float().sum(dim=0)
-            dist.all_reduce(bm)
-            eng.step(x, batch_mean=bm / n_global, n_global=n_global, update_stats=False, renorm_decoder=True, target=self._target)
-            if self._small is None or self._small.numel() != d_sae + 3:
-                self._small = torch.empty(d_sae + 3, dtype=torch.float32, device=x.device)
-            small = self._small
-            small[:d_sae].copy_(eng.fire_count)
-            small[d_sae:].copy_(eng.scalars[:3])
-            dist.all_reduce(eng.flat_g)
-            dist.all_reduce(small)                              # fire counts | loss, mse, l0 in one bucket
-            fire = small[:d_sae]
-            eng.scalars[:3].copy_(small[d_sae:])
-            eng.scalars[2] /= W
-            n_since_fired += 1
-            n_since_fired[fire > 0] = 0
-            act_freq_scores += fire
-            eng.grad_sqnorm()
-            eng.apply(lr, self.cfg.max_grad_norm)
-            return
-        bm = x.float().sum(dim=0)
-        dist.all_reduce(bm)                                     # global batch mean (sae.py:145)
-        if sae.cfg.use_ghost_grads and sae.training:
-            # top-k + ghost gradients (sae.py:151-179): the ghost term normalises by the residual's column mean and rescales by the mse
-            # loss of the WHOLE batch -- one more small all-reduce between the step and pv_sae_topk_ghost; the decoder renormalised in
-            # place (the ghost term reads W_dec as it lies), complete gradient buffers as every multi-rank step has them
-            dead = n_since_fired > sae.cfg.dead_feature_window
-            eng.renorm_decoder()
-            eng.step(x, batch_mean=bm / n_global, n_global=n_global, update_stats=False, renorm_decoder=False, want_out=True)
-            gl = torch.cat([(eng.sae_out[:x.shape[0]] - x).sum(dim=0), eng.scalars[1:2]])
-            dist.all_reduce(gl)
-            eng.topk_ghost(x, dead, ghost_global=(gl[:d_in] / n_global, gl[d_in:], n_global))
-        else:
-            eng.step(x, batch_mean=bm / n_global, n_global=n_global, update_stats=False, renorm_decoder=True)
-        shard = self._shard(eng.d_sae)
-        if self._small is None or self._small.numel() != d_in + d_sae + 3:
-            self._small = torch.empty(d_in + d_sae + 3, dtype=torch.float32, device=x.device)
-        small = self._small
-        small[:d_in].copy_(eng._g["b_dec"])
-        small[d_in:d_in + d_sae].copy_(eng.fire_count)
-        small[d_in + d_sae:].copy_(eng.scalars[:3])
-        if shard is None:
-            dist.all_reduce(eng.flat_g[:eng.n_flat - d_in])      # replicated optimizer: every rank needs every row
-        else:
-            for name in ("W_encT", "W_dec", "b_enc"):
-                self._reduce_scatter_rows(dist, eng._g[name], *shard)
-        dist.all_reduce(small)                                  # gb_dec | fire counts | loss, mse, l0 in one bucket
-        eng._g["b_dec"].copy_(small[:d_in])
-        fire = small[d_in:d_in + d_sae]
-        eng.scalars[:3].copy_(small[d_in + d_sae:])
-        eng.scalars[2] /= W                                     # l0 is a mean over tokens
-        n_since_fired += 1                                      # train_sae.py:356-361 on the global batch
-        n_since_fired[fire > 0] = 0
-        act_freq_scores += fire
-        if shard is None:
-            eng.grad_sqnorm()
-            eng.apply(lr, self.cfg.max_grad_norm)
-            return
-        j_lo, j_hi = shard
-        eng.grad_sqnorm_rows(j_lo, j_hi, include_b_dec=self.rank == 0)
-        dist.all_reduce(eng.scalars[3:4])                       # the clip norm is over the GLOBAL gradient
-        eng.apply(lr, self.cfg.max_grad_norm, j_lo, j_hi)       # this rank's rows (+ b_dec, identically everywhere)
-        self._pending = [dist.all_gather_into_tensor(full, full[j_lo:j_hi], async_op=True)
-                         for full in (eng.W_encT, eng.params["W_dec"], eng.params["b_enc"])]
 
     def _torch_step(self, sae, optimizer, scheduler, x, act_freq_scores, n_since_fired):
         """The reference algorithm on PyTorch autograd (CPU, ReLU/L1, ghost grads, ...)."""
