@@ -51,7 +51,9 @@ extern "C" {
  * 26: pv_vit_forward_from and pv_vit_forward_seg are gone -- pv_vit_forward_stage takes every segment they took).
  * Purely ADDITIVE exports do not bump it: the text tower (pv_text_desc, pv_text_weights, pv_text_plan_create,
  * pv_text_plan_set_weights, pv_text_forward), pv_attention and the logit lens (pv_logit_lens, pv_logit_lens_workspace_bytes,
- * PV_LENS_MAX_STACK) arrived at 25 and left every existing struct layout, signature, slot value and flag as it was; the Python binding checks the build id besides. */
+ * PV_LENS_MAX_STACK) arrived at 25 and left every existing struct layout, signature, slot value and flag as it was; the Python binding checks the build id besides.
+ * Likewise the head attribution (pv_head_attribution, pv_head_attribution_workspace_bytes, PV_ATTR_MAX_LAYERS,
+ * PV_ATTR_MAX_ANSWERS) at 26. */
 #define PV_ABI_VERSION 26
 int pv_abi_version(void);
 /* Hash of the sources this binary was built from (sha256 over the .hip / .hpp files of vit_prisma_amd/csrc and this header, names and
@@ -721,6 +723,44 @@ size_t pv_logit_lens_workspace_bytes(int32_t n_rows, int32_t n_stack, int32_t d_
 int pv_logit_lens(int32_t dtype, const void* const* resid, int32_t n_stack, int32_t n_rows, int32_t d_model, const float* scale,
                   const void* answers, int32_t n_answers, float* directions, int32_t* top_idx, float* top_logit, int32_t rank_of,
                   int32_t* rank, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Direct logit attribution by attention head (activation_cache.py: stack_head_results)        */
+/* ------------------------------------------------------------------------------------------ */
+
+/* Most layers of one call (the tap and W_O pointers travel to the kernels by value) and most answers of one call (the head
+ * kernel keeps a head's share of every answer in registers, so a tap is read once per call). */
+#define PV_ATTR_MAX_LAYERS  64
+#define PV_ATTR_MAX_ANSWERS 16
+
+/* Bytes of workspace pv_head_attribution needs: the folded answers G, fp32 [n_layers, n_answer_rows, n_heads * d_head].
+ * n_answer_rows = n_answers when the answers are shared, n_images * n_answers when each image has its own. */
+size_t pv_head_attribution_workspace_bytes(int32_t n_layers, int32_t n_heads, int32_t d_head, int32_t n_answer_rows);
+
+/* What einsum(stack_head_results(layer = n_layers, apply_ln = True), answers) computes (activation_cache.py:388-490: every head's
+ * z[..., h, :] @ W_O[h], stacked over the layers; :656-735: centred and divided by the cached hook_scale), without any
+ * [..., d_model] intermediate: the answers are centred and folded through W_O once (G, in the workspace), then one pass over
+ * the hook_z taps.  Everything is summed in fp32.
+ *   z           HOST array of n_layers device pointers, tap l = [n_images, n_tokens, n_heads, d_head] of `dtype`, contiguous,
+ *               16-byte aligned (blocks.l.attn.hook_z)
+ *   W_O         HOST array of n_layers device pointers, [n_heads, d_head, d_model] of `dtype`, contiguous, 16-byte aligned
+ *   pos         -1: every token; p >= 0: token p of every image alone (the output then has one token per image)
+ *   scale       [n_images * n_tokens] fp32: hook_scale of the LayerNorm the heads feed, always of all tokens
+ *   answers     fp32, 16-byte aligned: [n_answers, d_model] (per_image == 0) or [n_images, n_answers, d_model] (per_image != 0)
+ *   out         fp32 [n_images, T_out, n_layers * n_heads, n_answers], T_out = n_tokens or 1:
+ *               out[b, t, l * n_heads + h, o] = (sum_e z_l[b, t, h, e] G[l, g(b) + o, h * d_head + e]) / scale[b, t],
+ *               G[l, r, j] = sum_k W_O_l[j, k] (a[r, k] - mean_k a[r, :]),  g(b) = b * n_answers per image, else 0
+ *   workspace   16-byte aligned, pv_head_attribution_workspace_bytes
+ * A head whose z row holds a NaN or an infinity is NaN in every answer column of that head (as in the reference, whose mean is
+ * not finite then) and in no other head of the row: a dot product that is not finite is stored as NaN.
+ * Returns PV_ERR_INVALID with the rule in pv_last_error for: dtype other than PV_DTYPE_BF16, d_head outside {32, 64} and the
+ * multiples of 8 in (64, 128], d_model % 8 != 0, n_layers outside 1 .. PV_ATTR_MAX_LAYERS, n_answers outside
+ * 1 .. PV_ATTR_MAX_ANSWERS, pos outside -1 .. n_tokens - 1, a tap of 4 GiB or more; PV_ERR_WORKSPACE for a workspace below
+ * pv_head_attribution_workspace_bytes.  Allocates nothing. */
+int pv_head_attribution(int32_t dtype, const void* const* z, const void* const* W_O, int32_t n_layers,
+                        int32_t n_images, int32_t n_tokens, int32_t pos, int32_t n_heads, int32_t d_head, int32_t d_model,
+                        const float* scale, const float* answers, int32_t n_answers, int32_t per_image,
+                        float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

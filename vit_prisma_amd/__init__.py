@@ -15,9 +15,11 @@ from .vit import (Attention, Head, HookedViT, LayerNorm, LayerNormPre, MLP, Patc
 from .sae_vit import HookedSAEViT
 from .text import HookedTextTransformer
 from . import logit_lens
+from . import logit_attribution
+from .logit_attribution import head_logit_attribution
 
 __all__ = [
-    "logit_lens",
+    "logit_lens", "logit_attribution", "head_logit_attribution",
     "ActivationCache", "HookedViTConfig", "HookPoint", "LensHandle", "HookedRootModule", "HookedViT", "HookedSAEViT",
     "HookedTextTransformer", "HookedTextTransformerConfig",
     "Attention", "Head", "LayerNorm", "LayerNormPre", "MLP", "PatchEmbedding", "PosEmbedding",

@@ -139,6 +139,7 @@ EXPORTS = [
     "pv_debug_gemm_trace_arm", "pv_debug_gemm_trace_read", "pv_debug_set_tuning", "pv_debug_get_tuning",
     "pv_clip_preprocess",
     "pv_logit_lens_workspace_bytes", "pv_logit_lens",
+    "pv_head_attribution_workspace_bytes", "pv_head_attribution",
 ]
 
 
@@ -194,6 +195,10 @@ def lib() -> C.CDLL:
     L.pv_logit_lens_workspace_bytes.argtypes = [i32, i32, i32, i32]
     L.pv_logit_lens_workspace_bytes.restype = sz
     L.pv_logit_lens.argtypes = [i32, C.POINTER(vp), i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, sz, vp]
+    L.pv_head_attribution_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.pv_head_attribution_workspace_bytes.restype = sz
+    L.pv_head_attribution.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32,
+                                      vp, vp, sz, vp]
     if hasattr(L, "pv_sae_plan_create"):
         L.pv_sae_plan_create.argtypes = [C.POINTER(SaeDesc), C.POINTER(vp)]
         L.pv_sae_plan_destroy.argtypes = [vp]
