@@ -53,7 +53,8 @@ extern "C" {
  * pv_text_plan_set_weights, pv_text_forward), pv_attention and the logit lens (pv_logit_lens, pv_logit_lens_workspace_bytes,
  * PV_LENS_MAX_STACK) arrived at 25 and left every existing struct layout, signature, slot value and flag as it was; the Python binding checks the build id besides.
  * Likewise the head attribution (pv_head_attribution, pv_head_attribution_workspace_bytes, PV_ATTR_MAX_LAYERS,
- * PV_ATTR_MAX_ANSWERS) at 26. */
+ * PV_ATTR_MAX_ANSWERS) at 26, and the neuron attribution (pv_neuron_attribution, pv_neuron_attribution_topk,
+ * pv_neuron_attribution_workspace_bytes, PV_NATTR_MAX_K) at 26. */
 #define PV_ABI_VERSION 26
 int pv_abi_version(void);
 /* Hash of the sources this binary was built from (sha256 over the .hip / .hpp files of vit_prisma_amd/csrc and this header, names and
@@ -761,6 +762,56 @@ int pv_head_attribution(int32_t dtype, const void* const* z, const void* const* 
                         int32_t n_images, int32_t n_tokens, int32_t pos, int32_t n_heads, int32_t d_head, int32_t d_model,
                         const float* scale, const float* answers, int32_t n_answers, int32_t per_image,
                         float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Direct logit attribution by MLP neuron (activation_cache.py: stack_neuron_results)          */
+/* ------------------------------------------------------------------------------------------ */
+
+/* Most entries per (token, answer) the top-k form returns. */
+#define PV_NATTR_MAX_K 256
+
+/* Bytes of workspace both neuron-attribution calls need: the folded answers G, fp32 [n_layers, n_answer_rows, d_mlp].
+ * n_answer_rows = n_answers when the answers are shared, n_images * n_answers when each image has its own. */
+size_t pv_neuron_attribution_workspace_bytes(int32_t n_layers, int32_t d_mlp, int32_t n_answer_rows);
+
+/* What einsum(stack_neuron_results(layer = n_layers, apply_ln = True), answers) computes (activation_cache.py:523-654: every
+ * neuron's post[..., n, None] * W_out[n], stacked over the layers into [n_layers * d_mlp, B, T, d_model]; :656-735: centred and
+ * divided by the cached hook_scale), without any [..., d_model] intermediate: the answers are centred and folded through W_out
+ * once (G, in the workspace), then one elementwise pass over the mlp.hook_post taps.
+ *   post        HOST array of n_layers device pointers, tap l = [n_images, n_tokens, d_mlp] of `dtype`, contiguous, 16-byte
+ *               aligned (blocks.l.mlp.hook_post)
+ *   W_out       HOST array of n_layers device pointers, [d_mlp, d_model] of `dtype`, contiguous, 16-byte aligned
+ *   pos         -1: every token; p >= 0: token p of every image alone (the output then has one token per image)
+ *   scale       [n_images * n_tokens] fp32: hook_scale of the LayerNorm the neurons feed, always of all tokens
+ *   answers     fp32, 16-byte aligned: [n_answers, d_model] (per_image == 0) or [n_images, n_answers, d_model] (per_image != 0)
+ *   out         fp32, 16-byte aligned, [n_images, T_out, n_layers * d_mlp, n_answers], T_out = n_tokens or 1:
+ *               out[b, t, l * d_mlp + n, o] = fdiv(fmul(post_l[b, t, n], G[l, g(b) + o, n]), scale[b, t]), both rounded to nearest,
+ *               G[l, r, n] = sum_k W_out_l[n, k] (a[r, k] - mean_k a[r, :]),  g(b) = b * n_answers per image, else 0
+ *   workspace   16-byte aligned, pv_neuron_attribution_workspace_bytes
+ * A product that is not finite is stored as the NaN 0x7fc00000: a neuron whose post is NaN or an infinity is NaN in every answer
+ * column (as in the reference, whose mean over that neuron's result is not finite) and in no other neuron; post == 0 gives +-0.
+ * Returns PV_ERR_INVALID with the rule in pv_last_error for: dtype other than PV_DTYPE_BF16, d_mlp % 8 != 0, d_model % 8 != 0,
+ * n_layers outside 1 .. PV_ATTR_MAX_LAYERS, n_answers outside 1 .. PV_ATTR_MAX_ANSWERS, pos outside -1 .. n_tokens - 1, a tap of
+ * 4 GiB or more, a NULL or misaligned pointer; PV_ERR_WORKSPACE for a workspace below pv_neuron_attribution_workspace_bytes.
+ * Allocates nothing. */
+int pv_neuron_attribution(int32_t dtype, const void* const* post, const void* const* W_out, int32_t n_layers,
+                          int32_t n_images, int32_t n_tokens, int32_t pos, int32_t d_mlp, int32_t d_model,
+                          const float* scale, const float* answers, int32_t n_answers, int32_t per_image,
+                          float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The k largest of the n_layers * d_mlp values pv_neuron_attribution would store for every (output row, answer), without storing
+ * them: operands, workspace and refusals as above, and
+ *   k           1 .. PV_NATTR_MAX_K, at most n_layers * d_mlp
+ *   by          0: the key is the value; 1: the key is its magnitude
+ *   val, idx    fp32 / int32 [n_images, T_out, n_answers, k]: idx the flat index l * d_mlp + n, val the bits the dense call stores
+ *               there (the signed value, also with by = 1)
+ * Keys compare as floats: -0 equals +0 and a NaN is greater than everything, as torch.topk has it; ties go to the lowest flat
+ * index; the k entries are sorted by that order.  PV_ERR_INVALID also for k out of range and by outside {0, 1}. */
+int pv_neuron_attribution_topk(int32_t dtype, const void* const* post, const void* const* W_out, int32_t n_layers,
+                               int32_t n_images, int32_t n_tokens, int32_t pos, int32_t d_mlp, int32_t d_model,
+                               const float* scale, const float* answers, int32_t n_answers, int32_t per_image,
+                               int32_t k, int32_t by, float* val, int32_t* idx,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ composition one layer at a time) and beside the reference's helpers themselves (
 the whole [L H, B, T, d_model] stack), in the same process.
 
     python tools/attr_time.py [--images 512] [--answers 1] [--steps 10] [--torch-steps 2] [--warmup 2] [--rounds 2] [--no-helpers]
+    python tools/attr_time.py --neurons [--images 512] [--steps 10] [--torch-steps 1] [--rounds 2]      # by MLP neuron (below)
 
 Forms: shared answers [O, d] and per-image answers [B, O, d], each with pos=None (every token) and pos=0 (the CLS row).  Every form
 is warmed up before it is timed, a timed window is ``steps`` calls between two events, and the set is repeated ``rounds`` times in
@@ -25,6 +26,7 @@ ap.add_argument("--torch-steps", type=int, default=2)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--rounds", type=int, default=2)
 ap.add_argument("--no-helpers", action="store_true", help="skip the reference helpers' own composition (the full stack)")
+ap.add_argument("--neurons", action="store_true", help="time the attribution by MLP neuron (dense with pos=0, top-k over every token) instead")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "this tool measures on the GPU; there is no CPU substitute for its numbers"
 dev = torch.device("cuda:0")
@@ -82,6 +84,57 @@ with torch.no_grad():
             del cache.cache_dict[f"blocks.{l}.attn.hook_result"]
         eq = "cbtd,bod->cbto" if a.dim() == 3 else "cbtd,od->cbto"
         return torch.einsum(eq, stack, a).permute(1, 2, 0, 3)
+
+    def neuron_forms():
+        """--neurons: the dense form with pos=0 and one answer per image, the top-k form (k = 16) over every token with O = 1 and with
+        O = 4 shared answers; each beside the PyTorch path of the same call on the same cache.  Bytes: the mlp.hook_post taps once
+        (B T_out L d_mlp 2); the fold's operands (W_out, the answers) and G (L R d_mlp 4, read by every workgroup from the L2)
+        stand beside them."""
+        M = arch["d_mlp"]
+        a4 = 0.05 * torch.randn(4, d, device=dev, generator=gen) + 0.02
+        forms = [("dense", answers["per_image"][:, :1].contiguous(), 0, None), ("topk", answers["shared"][:1].contiguous(), None, 16),
+                 ("topk", a4, None, 16)]
+        for form, a, pos, k in forms:
+            t_out = T if pos is None else 1
+            n_ans = a.shape[-2]
+            tap_bytes = B * t_out * L * M * 2
+            out_bytes = B * t_out * L * M * n_ans * 4 if k is None else B * t_out * n_ans * k * 8
+            row = {"form": form, "images": B, "tokens": T, "layers": L, "d_mlp": M, "d_model": d, "answers": n_ans,
+                   "kind": "per_image" if a.dim() == 3 else "shared", "pos": pos, "k": k, "tap_mbytes": round(tap_bytes / 1e6, 1),
+                   "out_mbytes": round(out_bytes / 1e6, 2), "fold_mbytes": round((L * M * d * 2 + a.numel() * 4) / 1e6, 1),
+                   "g_mbytes": round(L * M * a.numel() / d * 4 / 1e6, 2),
+                   "gflop": round((2.0 * B * t_out * L * M * n_ans + 2.0 * L * M * d * a.numel() / d) / 1e9, 2)}
+            if k is None:
+                fn = lambda: logit_attribution.neuron_logit_attribution(cache, a, pos=pos, return_labels=False)      # noqa: E731
+            else:
+                fn = lambda: logit_attribution.top_neuron_logit_attribution(cache, a, k, pos=pos, by="abs")          # noqa: E731
+            native_ms, torch_ms = [], []
+            for _ in range(args.rounds):
+                logit_attribution.use_native(True)
+                native_ms.append(round(timed(fn, args.steps, args.warmup), 4))
+                assert logit_attribution.last_run_native
+            logit_attribution.use_native(True)
+            row["native_peak_mbytes"] = peak_mbytes(fn)
+            best = min(native_ms)
+            row.update(native_ms=native_ms, native_read_gbytes_per_s=round(tap_bytes / 1e6 / best, 1),
+                       native_gbytes_per_s=round((tap_bytes + out_bytes) / 1e6 / best, 1))
+            logit_attribution.use_native(False)
+            try:
+                for _ in range(args.torch_steps):               # (--torch-steps 0: the HIP path alone, for a kernel trace)
+                    torch_ms.append(round(timed(fn, 1, 0), 2))
+                    assert not logit_attribution.last_run_native
+                if torch_ms:
+                    row["pytorch_peak_mbytes"] = peak_mbytes(fn)
+                    row.update(pytorch_ms=torch_ms, pytorch_over_native=round(min(torch_ms) / best, 1))
+            except torch.cuda.OutOfMemoryError:
+                row["pytorch_ms"] = "out of memory at this shape"
+                torch.cuda.empty_cache()
+            logit_attribution.use_native(None)
+            print(json.dumps(row), flush=True)
+
+    if args.neurons:
+        neuron_forms()
+        sys.exit(0)
 
     for kind, a in answers.items():
         for pos in (None, 0):

@@ -16,10 +16,10 @@ from .sae_vit import HookedSAEViT
 from .text import HookedTextTransformer
 from . import logit_lens
 from . import logit_attribution
-from .logit_attribution import head_logit_attribution
+from .logit_attribution import head_logit_attribution, neuron_logit_attribution, top_neuron_logit_attribution
 
 __all__ = [
-    "logit_lens", "logit_attribution", "head_logit_attribution",
+    "logit_lens", "logit_attribution", "head_logit_attribution", "neuron_logit_attribution", "top_neuron_logit_attribution",
     "ActivationCache", "HookedViTConfig", "HookPoint", "LensHandle", "HookedRootModule", "HookedViT", "HookedSAEViT",
     "HookedTextTransformer", "HookedTextTransformerConfig",
     "Attention", "Head", "LayerNorm", "LayerNormPre", "MLP", "PatchEmbedding", "PosEmbedding",

@@ -140,6 +140,7 @@ EXPORTS = [
     "pv_clip_preprocess",
     "pv_logit_lens_workspace_bytes", "pv_logit_lens",
     "pv_head_attribution_workspace_bytes", "pv_head_attribution",
+    "pv_neuron_attribution_workspace_bytes", "pv_neuron_attribution", "pv_neuron_attribution_topk",
 ]
 
 
@@ -199,6 +200,12 @@ def lib() -> C.CDLL:
     L.pv_head_attribution_workspace_bytes.restype = sz
     L.pv_head_attribution.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32,
                                       vp, vp, sz, vp]
+    L.pv_neuron_attribution_workspace_bytes.argtypes = [i32, i32, i32]
+    L.pv_neuron_attribution_workspace_bytes.restype = sz
+    L.pv_neuron_attribution.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, vp, vp, i32, i32,
+                                        vp, vp, sz, vp]
+    L.pv_neuron_attribution_topk.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, vp, vp, i32, i32,
+                                             i32, i32, vp, vp, vp, sz, vp]
     if hasattr(L, "pv_sae_plan_create"):
         L.pv_sae_plan_create.argtypes = [C.POINTER(SaeDesc), C.POINTER(vp)]
         L.pv_sae_plan_destroy.argtypes = [vp]

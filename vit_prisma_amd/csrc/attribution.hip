@@ -29,15 +29,9 @@
 // (d + 1) u, the d_head products and their sum (d_head + 1) u, the division u:
 //   |got - exact| <= (2 d + d_head + 8) u sum_e |z_e| sum_k |W_ek| (|a_k| + mean_k |a_k|) / scale       (tests/_attribution_cases.py)
 // (products enter the sums by fmaf, one rounding per term, so the form is inside what the bound allows for mul + add.)
-#include "pv_common.hpp"
+#include "attribution.hpp"
 
 namespace {
-
-struct AttrPtrs {
-    const void* ptr[PV_ATTR_MAX_LAYERS];
-};
-
-constexpr int FOLD_TJ = 64, FOLD_TR = 16, FOLD_KC = 64, FOLD_WS = FOLD_KC + 4;   // W rows padded to 68 floats: 16-byte aligned, spread over the banks
 
 // grid = (ceil(HD / 64), ceil(R / 16), L); 256 threads: thread (jj = tid & 63, rg = tid >> 6) owns column j0 + jj of rows r0 + 4 rg .. + 3
 __global__ __launch_bounds__(256) void attr_fold_kernel(const AttrPtrs W_O, const float* __restrict__ answers, int HD, int d, int R,
@@ -218,6 +212,18 @@ bool attr_d_head_served(int d_head) {
 
 }  // namespace
 
+int attr_launch_fold(const char* who, const void* const* W, int n_layers, int64_t HD, int d_model, int64_t R, const float* answers,
+                     float* G, hipStream_t stream) {
+    AttrPtrs w{};
+    for (int l = 0; l < n_layers; ++l) w.ptr[l] = W[l];
+    const int64_t r_tiles = (R + FOLD_TR - 1) / FOLD_TR;
+    PV_REQUIRE(r_tiles <= 65535, std::string(who) + ": more than 65535 * 16 answer rows in one call");
+    const dim3 grid((unsigned)((HD + FOLD_TJ - 1) / FOLD_TJ), (unsigned)r_tiles, (unsigned)n_layers);
+    hipLaunchKernelGGL(attr_fold_kernel, grid, dim3(256), 0, stream, w, answers, (int)HD, d_model, (int)R, G);
+    PV_LAUNCH_CHECK("attr_fold_kernel");
+    return PV_OK;
+}
+
 extern "C" size_t pv_head_attribution_workspace_bytes(int32_t n_layers, int32_t n_heads, int32_t d_head, int32_t n_answer_rows) {
     if (n_layers <= 0 || n_heads <= 0 || d_head <= 0 || n_answer_rows <= 0) return 0;
     return (size_t)pv_align_up((int64_t)n_layers * n_answer_rows * n_heads * d_head * 4, 256);
@@ -255,15 +261,7 @@ extern "C" int pv_head_attribution(int32_t dtype, const void* const* z, const vo
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     float* G = reinterpret_cast<float*>(workspace);
 
-    {
-        AttrPtrs w{};
-        for (int l = 0; l < n_layers; ++l) w.ptr[l] = W_O[l];
-        const int64_t r_tiles = (R + FOLD_TR - 1) / FOLD_TR;
-        PV_REQUIRE(r_tiles <= 65535, "head attribution: more than 65535 * 16 answer rows in one call");
-        const dim3 grid((unsigned)((HD + FOLD_TJ - 1) / FOLD_TJ), (unsigned)r_tiles, (unsigned)n_layers);
-        hipLaunchKernelGGL(attr_fold_kernel, grid, dim3(256), 0, stream, w, answers, (int)HD, d_model, (int)R, G);
-        PV_LAUNCH_CHECK("attr_fold_kernel");
-    }
+    if (const int rc = attr_launch_fold("head attribution", W_O, n_layers, HD, d_model, R, answers, G, stream)) return rc;
 
     AttrHeadParams p{};
     for (int l = 0; l < n_layers; ++l) p.z.ptr[l] = z[l];
